@@ -15,7 +15,10 @@ queue, its kernels are confined to its half, its persistent stream-K launches ar
 1557 - 1630 for rounds 1 - 4's two plain streams sharing the whole chip (`--streams 2 --cu-split none`; `--streams 1` = strictly
 sequential frames on the whole chip). THE DETECTOR IS TRAINED FIRST (round 6): the `train_step` leg -- `--pretrain-iterations`
 captured SE-SSD iterations on fresh synthetic batches -- runs before anything else and its student's weights go into the timed
-engines (`--random-weights`: rounds 1 - 5's seeded random weights; `--weights FILE`: a saved state_dict). One JSON line on rank 0:
+engines (`--random-weights`: rounds 1 - 5's seeded random weights; `--weights FILE`: a saved state_dict). One JSON line on rank 0
+(metric / value / unit / higher_is_better / dtype / ms_per_step / config, and train_step when the detector was trained in the
+process). A plain run does only that: set up, warm up, time the K steps, print. `--dump-outputs DIR` writes the detections of the
+last timed step as DIR/*.npy (same arguments, same input frames). Everything below except train_step needs `--full`:
   parity        THE TIMED CONFIGURATION held to the oracle before the clock starts: the frames of the cpu_baseline sample go
                 through the very engines that are timed (autotuned tilings, stream-K workgroup counts, captured graphs) and
                 every detection is compared with the oracle's under oracle/compare.py's STRICT rule (trained weights: 2 mm / 2 mrad
@@ -33,7 +36,8 @@ engines (`--random-weights`: rounds 1 - 5's seeded random weights; `--weights FI
                 strictly sequential latency mode (informational, never `value`)
   cpu_baseline  the CPU oracle pipeline (port of the reference path: the reference itself cannot run here) on a
                 bounded sample of the same frames, on this box's host cores.
-  train_step    BASELINE configs[2]: ms per replay of the captured SE-SSD training iteration (informational)
+  train_step    BASELINE configs[2]: ms per replay of the captured SE-SSD training iteration (informational; measured by the
+                training that precedes a plain run, or as a leg of its own under --full with --random-weights / --weights)
 `--stress` = BASELINE configs[4] (200k points, 64k voxels, batch 8), `--batch B` = B frames per step.
 """
 import argparse
@@ -127,6 +131,13 @@ def parse(argv=None):
     ap.add_argument("--no-offset-split", action="store_true", help="autotune without the offset-split sparse conv variants")
     ap.add_argument("--no-streamk", action="store_true", help="autotune without the stream-K Winograd variants")
     ap.add_argument("--wino-cfg", type=int, default=0, help="force this tile_cfg (20-25) on the seven 3x3 stride-1 SSFA layers after autotune")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the cpu_baseline sample and the parity gate, value_sequential, the "
+                         "roofline legs, host_io and the informational train_step leg (each still switched off by its own --no-* / "
+                         "--cpu-frames 0). Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the detections of the last timed step (what a caller of the timed path "
+                         "receives) as DIR/<name>.npy in float32")
     args = ap.parse_args(argv)
     if args.stress:
         args.points, args.max_voxels, args.batch, args.supersample, args.pool = 200000, 64000, 8, 3, 8
@@ -148,6 +159,19 @@ def free_port():
     p = s.getsockname()[1]
     s.close()
     return p
+
+
+def dump_outputs(path, results):
+    """--dump-outputs: the per-frame results of one step (engine.results(): box3d_lidar (n, 7), scores (n,), label_preds (n,)),
+    the frames of the batch concatenated in slot order, as float32 .npy files; detections_per_frame splits them again."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"box3d_lidar": np.concatenate([np.asarray(r["box3d_lidar"], np.float32).reshape(-1, 7) for r in results]),
+              "scores": np.concatenate([np.asarray(r["scores"], np.float32).reshape(-1) for r in results]),
+              "label_preds": np.concatenate([np.asarray(r["label_preds"], np.float32).reshape(-1) for r in results]),
+              "detections_per_frame": np.array([len(r["scores"]) for r in results], np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return arrays
 
 
 def default_engine_factory(args, dev, model=None, count=None):
@@ -464,14 +488,15 @@ def run_rank(args, rank=0, world=1, local_rank=0, backend="nccl", device=None, e
     n_sets = (parts if masked else 1)
     tokens = [None] * n_sets     # per CU set: the event the last dense stage (back graph) of the set recorded
 
-    # ---- CPU oracle sample (cpu_baseline) and the parity gate on the configuration that is about to be timed
+    # ---- CPU oracle sample (cpu_baseline) and the parity gate on the configuration that is about to be timed (--full only)
+    full = bool(getattr(args, "full", False))
     cpu_base, parity = None, None
-    if args.cpu_frames > 0 and world == 1 and rank == 0 and on_gpu:
+    if full and args.cpu_frames > 0 and world == 1 and rank == 0 and on_gpu:
         cpu_base, sample = oracle_sample(args, model, frames_np)
         parity = parity_gate(args, engines, streams, frames, sample)  # at ANY batch size (round 3 skipped it at batch > 1)
         log("parity:", {k: v for k, v in parity.items() if k != "rule"})
         del sample
-    elif args.cpu_frames > 0 and world > 1 and on_gpu:
+    elif full and args.cpu_frames > 0 and world > 1 and on_gpu:
         # N > 1 (round-4 review item: no multi-GPU result was ever held to the oracle; every rank autotunes on its own): EVERY rank
         # holds its own timed engines to the oracle on a SHORT sample of its own frames -- all ranks at the same time, so nobody
         # waits at the barrier for rank 0 --, the verdicts are summed over the ranks and rank 0 reports them. The cpu_baseline
@@ -521,7 +546,7 @@ def run_rank(args, rank=0, world=1, local_rank=0, backend="nccl", device=None, e
             n_collectives[0] += 1
         sync()
 
-    # The oracle sample above leaves the GPU idle for tens of seconds: before the W warm-up steps the clocks are brought back up
+    # The oracle sample above (--full) leaves the GPU idle for tens of seconds: before the W warm-up steps the clocks are brought back up
     # by running frames for a fixed wall time (untimed, like the warm-up; the driver's W may be as small as 5 frames = 4 ms)
     if on_gpu:
         spin_until = time.perf_counter() + args.spinup_seconds
@@ -560,6 +585,9 @@ def run_rank(args, rank=0, world=1, local_rank=0, backend="nccl", device=None, e
     dets = int(eng.out["count"][0].item())
     if int(eng.err.item()) != 0:
         raise SystemExit("sparse capacity overflow during the benchmark: results invalid")
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        # before any --full leg re-runs the engines: the detections of the LAST timed step, as its engine left them
+        dump_outputs(args.dump_outputs, engines[(args.steps - 1) % len(engines)].results())
 
     out = None
     if rank == 0:
@@ -616,7 +644,7 @@ def run_rank(args, rank=0, world=1, local_rank=0, backend="nccl", device=None, e
                                  parity_identical=int(parity["identical"]), parity_rule=parity["rule_set"],
                                  parity_bev_rel_err=parity["bev_rel_err"], parity_max_centre_abs_diff_m=parity.get("max_centre_abs_diff_m"),
                                  parity_max_score_rel_diff=parity.get("max_score_rel_diff"))
-    if rank == 0 and on_gpu:
+    if rank == 0 and on_gpu and full:
         # ---- the same engines strictly one frame at a time (informational; the driver's record then holds both figures)
         seq_eng, seq_st = eng, streams[0]
         if masked and world == 1 and (not args.no_sequential or not args.no_roofline):

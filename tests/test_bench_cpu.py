@@ -116,6 +116,35 @@ def test_single_rank_no_process_group():
     assert out["n_gpus"] == 1 and out["config"]["records_gathered"] == 5 and "parity" not in out
 
 
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the detections of the LAST timed step (its engine's results()) as float32 .npy files; --full is off by
+    default and a plain line carries none of the --full legs"""
+    sys.path[:0] = [ROOT]
+    import bench
+    steps, streams = 5, 2
+    argv = ["--steps", str(steps), "--warmup", "1", "--eager", "--no-autotune", "--points", "300", "--pool", "4", "--streams", str(streams),
+            "--dump-outputs", str(tmp_path / "out")]
+    args = bench.parse(argv)
+    assert not args.full and bench.parse(argv + ["--full"]).full
+    made = {}
+
+    def factory(a, dev):
+        made["engines"] = [StubEngine(dev) for _ in range(max(1, a.streams))]
+        return None, made["engines"]
+
+    out = bench.run_rank(args, 0, 1, 0, backend="gloo", device="cpu", engine_factory=factory)
+    assert out["steps"] == steps and out["ms_per_step"] > 0
+    for k in ("parity", "cpu_baseline", "roofline", "value_sequential", "host_io"):
+        assert k not in out
+    want = made["engines"][(steps - 1) % streams].results()
+    got = {n: np.load(str(tmp_path / "out" / (n + ".npy"))) for n in ("box3d_lidar", "scores", "label_preds", "detections_per_frame")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["detections_per_frame"].tolist() == [len(r["scores"]) for r in want]
+    assert np.array_equal(got["box3d_lidar"], np.concatenate([r["box3d_lidar"] for r in want]).reshape(-1, 7))
+    assert np.array_equal(got["scores"], np.concatenate([r["scores"] for r in want]))
+    assert np.array_equal(got["label_preds"], np.concatenate([r["label_preds"] for r in want]).astype(np.float32))
+
+
 def test_help_text_formats(capsys):
     """argparse %-formats every help string: a bare per-cent sign in one of them broke `bench.py --help` for two rounds"""
     sys.path[:0] = [ROOT]

@@ -35,7 +35,7 @@ def test_two_ranks_each_hold_their_engines_to_the_oracle(streams):
     sets); here both ranks share the one GPU, so eight engines run on the two halves"""
     world, steps = 2, 8
     argv = ["--gpus", str(world), "--steps", str(steps), "--warmup", "2", "--streams", str(streams), "--cpu-frames", "3", "--no-roofline",
-            "--no-host-io", "--no-sequential", "--no-train-step", "--pool", "4", "--spinup-seconds", "0.1"]
+            "--no-host-io", "--no-sequential", "--no-train-step", "--pool", "4", "--spinup-seconds", "0.1", "--full"]
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
@@ -64,12 +64,12 @@ def test_two_ranks_each_hold_their_engines_to_the_oracle(streams):
 
 
 def test_two_ranks_train_first_and_gate_strictly():
-    """the driver's command at N > 1 (`bench.py --gpus N --steps K --warmup W`, no other flag): every rank trains the detector in its
+    """the driver's command at N > 1 with its checks (`bench.py --gpus N --steps K --warmup W --full`): every rank trains the detector in its
     own process BEFORE the process group exists (the captured iteration of a one-rank job: no SyncBN, one graph), then joins the
     group, builds its engines on CU-masked streams, and gates them under the STRICT rule on a sample of its own frames"""
     world, steps = 2, 8
     argv = ["--gpus", str(world), "--steps", str(steps), "--warmup", "2", "--cpu-frames", "3", "--no-roofline", "--no-host-io", "--no-sequential",
-            "--pool", "4", "--spinup-seconds", "0.1", "--train-replays", "2"]
+            "--pool", "4", "--spinup-seconds", "0.1", "--train-replays", "2", "--full"]
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()

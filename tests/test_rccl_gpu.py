@@ -40,7 +40,7 @@ def test_collectives_on_masked_streams_and_ordered_teardown():
 
 
 BENCH = ["bench.py", "--gpus", "1", "--steps", "12", "--warmup", "4", "--cpu-frames", "2", "--no-train-step", "--no-host-io",
-         "--no-roofline", "--no-sequential", "--pool", "4", "--spinup-seconds", "0.1"]
+         "--no-roofline", "--no-sequential", "--pool", "4", "--spinup-seconds", "0.1", "--full"]
 
 
 def test_bench_rank_over_nccl_exits_cleanly():

@@ -487,7 +487,8 @@ int sessd_conv3x3_winograd(const float* in, int batch, int cin, int h, int w, co
  * tap_offsets[t]] (element strides / offsets, ntaps <= 16, tap_offsets a HOST array): a transposed, flipped or tap-selected view
  * of the stored weight without an intermediate tensor. sessd_conv3x3_winograd_pack: U = G g G^T of the 3x3 filters of the same
  * kind of view (flip != 0: the adjoint layer), written in the layout of sessd_conv3x3_winograd (layout 0) or of
- * sessd_conv3x3_winograd_sk shape 0 / 1 (layout 1 / 2), padding included. */
+ * sessd_conv3x3_winograd_sk shape 0 / 1 / 2 / 3 (layout 1 / 2 / 3 / 4; layout 4 = three bfloat16 planes, cin % 16 == 0), padding
+ * included. */
 int sessd_conv2d_pack_taps(const float* w, long long out_stride, long long in_stride, const int* tap_offsets, int ntaps, int cout,
                            int cin, float* out, sessd_stream_t stream);
 int sessd_conv3x3_winograd_pack(const float* w, long long out_stride, long long in_stride, int flip, int cout, int cin, int layout,
@@ -496,7 +497,9 @@ int sessd_conv3x3_winograd_pack(const float* w, long long out_stride, long long 
  * transform runs once per tile block instead of once per 32-cout block) and the rounds of all units are dealt out "stream-K" in
  * equal shares to `workgroups` persistent workgroups (a multiple of 8; 0 = the shape's default), units cut by a share boundary
  * being finished by whichever part arrives last. shape 0: 8 waves x 128 couts per workgroup, one per CU; shape 1: 4 waves x 64
- * couts, two per CU. upk = U = G g G^T packed [ceil(cout / C)][cin/2][NW][2][32][C/32][16/NW], (NW, C) = (8, 128) / (4, 64);
+ * couts, two per CU; shape 2: 4 waves x 128 couts (output transform in registers); shape 3: shape 0 on the bf16 matrix cores at
+ * f32 accuracy (operands split into three bf16 terms, six products kept; upk = layout 4 of sessd_conv3x3_winograd_pack).
+ * upk = U = G g G^T packed [ceil(cout / C)][cin/2][NW][2][32][C/32][16/NW], (NW, C) = (8, 128) / (4, 64);
  * cin % (2 NW) == 0, even H and W. workspace: sessd_conv3x3_winograd_sk_workspace_bytes(...) bytes, zeroed ONCE by the caller
  * (the kernel leaves its counters zero), not shared between launches that may run concurrently. */
 size_t sessd_conv3x3_winograd_sk_workspace_bytes(int batch, int h, int w, int cout, int shape, int workgroups);
@@ -526,7 +529,7 @@ int sessd_conv3x3_winograd_sk_sets(const float* in, int batch, int nsets, int ci
  *   sessd_fill_inactive_tiles   out[b][co][tile] = value[co] (the layer's constant, computed by the host from the folded weights;
  *                               one value per output parity class for job.tile = 4 / 6) in the tiles nobody computes, up to 12
  *                               layers per launch
- *   sessd_conv3x3_winograd_sk_active   sessd_conv3x3_winograd_sk over the listed tiles only (same packed U, same workspace; the
+ *   sessd_conv3x3_winograd_sk_active   sessd_conv3x3_winograd_sk (shape 0, 1 or 3) over the listed tiles only (same packed U, same workspace; the
  *                               shares of the round list are sized on the device, workgroups beyond rounds / min_rounds exit;
  *                               min_rounds = -k: whole-unit shares of at least k units, no unit cut, no partial sums in memory)
  * Results equal the dense layer's to float32 rounding (tests/test_dense_active_gpu.py); replaces nothing in the reference -- it is

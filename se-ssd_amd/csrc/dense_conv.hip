@@ -923,8 +923,15 @@ __global__ __launch_bounds__(256) void pack_taps_kernel(PackArgs A, float* __res
 // layout 1: sessd_conv3x3_winograd_sk shape 0  [ceil(co/128)][ci/2][8][2][32][4][2]
 // layout 2: sessd_conv3x3_winograd_sk shape 1  [ceil(co/64)][ci/2][4][2][32][2][4]
 // layout 3: sessd_conv3x3_winograd_sk shape 2  [ceil(co/128)][ci/2][wave 4][2][32][xi 16]
+// layout 4: sessd_conv3x3_winograd_sk shape 3  three bf16 planes u = u0 + u1 + u2 (each rounded to nearest from the residual of
+//           the previous one), [ceil(co/128)][wave = xi/2][step = (ci/16) * 8 + xi%2 * 4 + (co/32)%4][plane 3]
+//           [lane = (ci/8)%2 * 32 + co%32][ci%8]
+__device__ __forceinline__ unsigned short bf16_rne_bits(float x) {
+  const unsigned u = __builtin_bit_cast(unsigned, x);
+  return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
 __device__ __forceinline__ void winograd_pack_body(const PackArgs& A, int flip, int layout, float* __restrict__ out, size_t idx) {
-  const int cpad = layout == 0 ? A.cp : ((layout == 1 || layout == 3) ? (A.co + 127) / 128 * 128 : (A.co + 63) / 64 * 64);
+  const int cpad = layout == 0 ? A.cp : ((layout == 1 || layout == 3 || layout == 4) ? (A.co + 127) / 128 * 128 : (A.co + 63) / 64 * 64);
   if (idx >= (size_t)cpad * A.ci) return;
   const int o = (int)(idx % cpad), c = (int)(idx / cpad);
   double g[3][3];
@@ -953,6 +960,20 @@ __device__ __forceinline__ void winograd_pack_body(const PackArgs& A, int flip, 
     for (int b = 0; b < 4; ++b) {
       const int xi = a * 4 + b;
       size_t dst;
+      if (layout == 4) {
+        const int grp = o >> 7, cb = (o >> 5) & 3, i = o & 31, wave = xi >> 1, xl = xi & 1;
+        const size_t step = (size_t)(c >> 4) * 8 + xl * 4 + cb;
+        dst = ((((size_t)grp * 8 + wave) * (size_t)(A.ci >> 1) + step) * 3) * 512 + (size_t)(((c >> 3) & 1) * 32 + i) * 8 + (c & 7);
+        unsigned short* o16 = reinterpret_cast<unsigned short*>(out);
+        const float f = (float)u[b];
+        const unsigned short t0 = bf16_rne_bits(f);
+        const float r = f - __builtin_bit_cast(float, (unsigned)t0 << 16);
+        const unsigned short t1 = bf16_rne_bits(r);
+        o16[dst] = t0;
+        o16[dst + 512] = t1;
+        o16[dst + 1024] = bf16_rne_bits(r - __builtin_bit_cast(float, (unsigned)t1 << 16));
+        continue;
+      }
       if (layout == 0) {
         dst = ((((size_t)kp * 4 + (xi >> 2)) * 2 + h) * cpad + o) * 4 + (xi & 3);
       } else if (layout == 1) {
@@ -1028,14 +1049,15 @@ int sessd_conv2d_pack_taps(const float* w, long long out_stride, long long in_st
 }
 
 // U = G g G^T of a 3x3 weight viewed through (out_stride, in_stride, flip) as above, in the layout of sessd_conv3x3_winograd
-// (layout 0) or sessd_conv3x3_winograd_sk shape 0 / 1 (layout 1 / 2); `out` must hold the padded layout (all of it is written).
+// (layout 0) or sessd_conv3x3_winograd_sk shape 0 / 1 / 2 / 3 (layout 1 / 2 / 3 / 4: three bf16 planes, cin % 16 == 0); `out` must
+// hold the padded layout (all of it is written).
 int sessd_conv3x3_winograd_pack(const float* w, long long out_stride, long long in_stride, int flip, int cout, int cin, int layout,
                                 float* out, hipStream_t stream) {
-  if (cout < 1 || cin < 2 || (cin & 1) || layout < 0 || layout > 3) return SESSD_EINVAL;
+  if (cout < 1 || cin < 2 || (cin & 1) || layout < 0 || layout > 4 || (layout == 4 && cin % 16)) return SESSD_EINVAL;
   PackArgs A;
   A.w = w; A.so = out_stride; A.sc = in_stride; A.co = cout; A.ci = cin; A.nt = 9; A.cp = sessd_divup(cout, 32) * 32;
   for (int t = 0; t < 16; ++t) A.tap_off[t] = 0;
-  const int cpad = layout == 0 ? A.cp : ((layout == 1 || layout == 3) ? sessd_divup(cout, 128) * 128 : sessd_divup(cout, 64) * 64);
+  const int cpad = layout == 0 ? A.cp : ((layout == 1 || layout == 3 || layout == 4) ? sessd_divup(cout, 128) * 128 : sessd_divup(cout, 64) * 64);
   const size_t total = (size_t)cpad * cin;
   SESSD_LAUNCH(winograd_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, A, flip, layout, out);
   SESSD_CHECK_LAUNCH();

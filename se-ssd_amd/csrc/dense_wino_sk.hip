@@ -24,6 +24,18 @@
 //               -- if that made it the last after all, it re-reads all parts in share order. No workgroup ever waits for
 //               another. Summation order is fixed (share order), so results do not depend on arrival order.
 // Numerics: Winograd rounding (1e-6 of the output scale); the bits depend on (shape, number of workgroups), not on timing.
+//
+// SPLIT (shape 3: 8 waves x 128 couts): the same units, rounds, shares, cut-unit exchange and epilogue, but the GEMMs run on the
+// bf16 matrix cores at f32 accuracy. Every f32 operand is split into three bf16 terms, a = a0 + a1 + a2 (each rounded to nearest
+// from the residual of the previous one; the residuals are exact), and of the nine products of a pair the six with i + j <= 2
+// are kept -- the three dropped are below ~2^-23 |a b|, the size of f32 rounding. A round (16 input channels) is one K = 16
+// v_mfma_f32_32x32x16_bf16 per accumulator and product: 48 per wave at 32 cycles against 64 f32 MFMAs at 64 cycles.
+//   U : host-packed as three bf16 planes [cout group][wave 8][step = round * 8 + x * 4 + cb][plane 3][lane 64][8 channels]: the
+//       operands of one (accumulator, step) are three 1 KB loads; a ring of 4 steps, loaded 3 steps ahead.
+//   V : lane (tile j, row pair h) of wave w loads rows (P, Q, S) = (0, 2, 1) / (2, 1, 3) of BOTH channels of k-step w, forms
+//       transform rows 2h (P - Q) and 2h + 1 (Q +- S) -- the f32 transform's values, bit for bit -- and writes the split channel
+//       pairs as 32-bit words into LDS [plane 3][xi 16][channel half 2][tile 32][8 channels] (48 KB per buffer).
+//   MFMA order per accumulator and round, smallest terms first: a2b0, a1b1, a0b2, a1b0, a0b1, a0b0.
 #include <cstdlib>
 #include "common.hpp"
 
@@ -33,6 +45,8 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x4v = __attribute__((ext_vector_type(4))) float;
 using f32x2v = __attribute__((ext_vector_type(2))) float;
 typedef unsigned int u32x4g __attribute__((__vector_size__(16)));  // the b128 buffer builtins' own type
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 __device__ __forceinline__ rsrc_t make_rsrc(const void* base, unsigned bytes) {
@@ -50,6 +64,18 @@ __device__ __forceinline__ float sadd(float a, float b) {
   float r;
   asm volatile("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
+}
+
+// (x0, x1) -> three packed bf16 pairs with x = t0 + t1 + t2 (round to nearest at every step; the residuals are exact in f32)
+__device__ __forceinline__ unsigned pk_bf16(float x0, float x1) {
+  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2v){x0, x1}, bf16x2));
+}
+__device__ __forceinline__ void split3_pk(float x0, float x1, unsigned& t0, unsigned& t1, unsigned& t2) {
+  t0 = pk_bf16(x0, x1);
+  x0 -= __builtin_bit_cast(float, t0 << 16); x1 -= __builtin_bit_cast(float, t0 & 0xFFFF0000u);
+  t1 = pk_bf16(x0, x1);
+  x0 -= __builtin_bit_cast(float, t1 << 16); x1 -= __builtin_bit_cast(float, t1 & 0xFFFF0000u);
+  t2 = pk_bf16(x0, x1);
 }
 
 struct WinoArgs {
@@ -75,17 +101,20 @@ struct WinoArgs {
 // VAR: measured code variants of the main loop (same arithmetic, same results; `SESSD_WINO_VAR` selects one at launch for
 // A/B runs, 0 ships): bit 0 = the patch transform with scalar adds instead of packed v_pk_add_f32 (MI355X_MICROARCH.md
 // measures packed adds beside MFMAs as an anti-lever), bit 1 = s_setprio around the MFMA groups.
-template <int NW, int CBN, int VAR = 0, bool LIST = false>
+template <int NW, int CBN, int VAR = 0, bool LIST = false, bool SPLIT = false>
 __global__ __launch_bounds__(NW * 64, 8 / NW) void conv3x3s1_winograd_sk_kernel(WinoArgs A) {
   constexpr int XW = 16 / NW;                          // transform points per wave
   static_assert(XW * CBN == 8, "8 accumulators per wave");
+  static_assert(!SPLIT || (NW == 8 && VAR == 0), "the split main loop is written for 8 waves (a round = one K = 16 MFMA)");
+  constexpr int VBUF_S = 3 * 16 * 64 * 4;              // SPLIT: floats of one V buffer, [plane 3][xi 16][lane 64][8 bf16]
   constexpr int NT = NW * 64;
   constexpr unsigned WSTEP = NW * 2u * 32u * 32u;      // bytes of packed U per k-step
   constexpr int VBUF = NW * 1024;                      // floats of one V buffer: [ks NW][xi 16][h 2][tile 32]
   constexpr int SLOT = CBN * 32 * 32 * 4;              // floats of one scratch slot
   constexpr int NPT = 1024 / NT;                       // (cout, tile) pairs per thread and 32-cout pass
   constexpr int RING = NW;                             // U operand sets in flight (one round's worth)
-  __shared__ __attribute__((aligned(16))) float lds[16384];  // 64 KB: V double buffer, then the M exchange of the epilogue
+  // 64 KB (SPLIT 96 KB): V double buffer, then the M exchange of the epilogue
+  __shared__ __attribute__((aligned(16))) float lds[SPLIT ? 2 * VBUF_S : 16384];
   __shared__ int s_last, s_pend;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -255,6 +284,19 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void conv3x3s1_winograd_sk_kernel(
     f32x4v pr[4];
     f32x4v ua[RING][2];
     float bv[2][XW];
+    // SPLIT: rows (P, Q, S) of both channels, U ring of 4 steps x 3 planes, V of the current point (3 planes)
+    f32x4v ps[2][3];
+    bf16x8 us[4][3], bs[3];
+    unsigned rs[3] = {SESSD_OOB, SESSD_OOB, SESSD_OOB};
+    if constexpr (SPLIT) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const int y = y0 + (q == 0 ? 2 * h : (q == 1 ? 2 - h : 1 + 2 * h));
+        rs[q] = (tlive && y >= 0 && y < A.hin) ? img_off + (unsigned)((y * A.win + max(x0, 0)) * 4) : SESSD_OOB;
+      }
+    }
+    const rsrc_t wrs = SPLIT ? make_rsrc(A.upk + (size_t)wset * A.upk_stride + (size_t)cg * A.cin * 3072, (unsigned)A.cin * 12288u) : wr;
+    const unsigned wso = SPLIT ? (unsigned)(wave * A.cin * 1536 + lane * 16) : 0u;
 
 #define SESSD_SK_LOADP(ROUND)                                                                      \
   {                                                                                                \
@@ -341,15 +383,110 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void conv3x3s1_winograd_sk_kernel(
     voff ^= VBUF;                                                                                  \
     ++rr;                                                                                          \
   }
+  // ---- SPLIT main loop (see the header): same rounds, step s = accumulator (x = s / 4, cb = s % 4) instead of k-step; V of
+  // point x read at the step that starts it, the patches of the next round loaded with the second half of the round
+#define SESSD_SS_LOADP(ROUND)                                                                      \
+  {                                                                                                \
+    const unsigned xs = (unsigned)(min((ROUND), r1 - 1) * NW + wave) * xstep;                      \
+    _Pragma("unroll") for (int c = 0; c < 2; ++c)                                                  \
+      _Pragma("unroll") for (int q = 0; q < 3; ++q)                                                \
+        ps[c][q] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(xr, (int)rs[q], (int)(xs + c * (xstep >> 1)), 0)); \
+  }
+#define SESSD_SS_LOADU(SET, KG)                                                                    \
+  {                                                                                                \
+    const unsigned ws = (unsigned)min((KG), klast) * 3072u;                                        \
+    _Pragma("unroll") for (int p = 0; p < 3; ++p)                                                  \
+      us[SET][p] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, (int)(wso + 1024u * p), (int)ws, 0)); \
+  }
+#define SESSD_SS_TRANSFORM(VOFF)                                                                   \
+  {                                                                                                \
+    if (edge) {                                                                                    \
+      _Pragma("unroll") for (int c = 0; c < 2; ++c)                                                \
+        _Pragma("unroll") for (int q = 0; q < 3; ++q) {                                            \
+          const f32x4v p = ps[c][q];                                                               \
+          ps[c][q].x = mask_l ? 0.f : p.x; ps[c][q].y = mask_l ? p.x : p.y;                        \
+          ps[c][q].z = mask_l ? p.y : p.z; ps[c][q].w = mask_l ? p.z : (mask_r ? 0.f : p.w);       \
+        }                                                                                          \
+    }                                                                                              \
+    float vt[2][8];                                                                                \
+    _Pragma("unroll") for (int c = 0; c < 2; ++c) {                                                \
+      const f32x4v ra = ps[c][0] - ps[c][1];                                                       \
+      const f32x4v rb = ps[c][1] + (h ? -ps[c][2] : ps[c][2]);                                     \
+      vt[c][0] = ra.x - ra.z; vt[c][1] = ra.y + ra.z; vt[c][2] = ra.z - ra.y; vt[c][3] = ra.y - ra.w; \
+      vt[c][4] = rb.x - rb.z; vt[c][5] = rb.y + rb.z; vt[c][6] = rb.z - rb.y; vt[c][7] = rb.y - rb.w; \
+    }                                                                                              \
+    unsigned* dst = reinterpret_cast<unsigned*>(&lds[(VOFF) + ((8 * h) * 64 + (wave >> 2) * 32 + j) * 4 + (wave & 3)]); \
+    _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                \
+      unsigned t0, t1, t2;                                                                         \
+      split3_pk(vt[0][e], vt[1][e], t0, t1, t2);                                                   \
+      dst[e * 256] = t0; dst[(16 + e) * 256] = t1; dst[(32 + e) * 256] = t2;                       \
+    }                                                                                              \
+  }
+#define SESSD_SS_READV(VOFF, X)                                                                    \
+  {                                                                                                \
+    _Pragma("unroll") for (int p = 0; p < 3; ++p)                                                  \
+      bs[p] = __builtin_bit_cast(bf16x8, *static_cast<const u32x4g*>(__builtin_assume_aligned(                    \
+          &lds[(VOFF) + ((p * 16 + wave * XW + (X)) * 64 + lane) * 4], 16)));                     \
+  }
+#define SESSD_SS_MMA(SET, S)                                                                       \
+  {                                                                                                \
+    f32x16 a_ = acc[(S) >> 2][(S) & 3];                                                            \
+    a_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(us[SET][2], bs[0], a_, 0, 0, 0);                  \
+    a_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(us[SET][1], bs[1], a_, 0, 0, 0);                  \
+    a_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(us[SET][0], bs[2], a_, 0, 0, 0);                  \
+    a_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(us[SET][1], bs[0], a_, 0, 0, 0);                  \
+    a_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(us[SET][0], bs[1], a_, 0, 0, 0);                  \
+    a_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(us[SET][0], bs[0], a_, 0, 0, 0);                  \
+    acc[(S) >> 2][(S) & 3] = a_;                                                                   \
+  }
+#define SESSD_SS_STEP(KS)                                                                          \
+  {                                                                                                \
+    SESSD_SS_LOADU(((KS) + 3) & 3, kg0 + (KS) + 3)                                                 \
+    __builtin_amdgcn_sched_barrier(0);                                                             \
+    SESSD_SS_MMA((KS) & 3, KS)                                                                     \
+    __builtin_amdgcn_sched_barrier(0);                                                             \
+  }
+#define SESSD_SS_ROUND()                                                                           \
+  {                                                                                                \
+    const int kg0 = rr * 8;                                                                        \
+    SESSD_SS_READV(voff, 0)                                                                        \
+    __builtin_amdgcn_sched_barrier(0);                                                             \
+    SESSD_SS_STEP(0)                                                                               \
+    SESSD_SS_STEP(1)                                                                               \
+    SESSD_SS_STEP(2)                                                                               \
+    SESSD_SS_STEP(3)                                                                               \
+    SESSD_SS_LOADP(rr + 1)                                                                         \
+    SESSD_SS_READV(voff, 1)                                                                        \
+    __builtin_amdgcn_sched_barrier(0);                                                             \
+    SESSD_SS_STEP(4)                                                                               \
+    SESSD_SS_STEP(5)                                                                               \
+    SESSD_SS_STEP(6)                                                                               \
+    SESSD_SS_STEP(7)                                                                               \
+    SESSD_SS_TRANSFORM(voff ^ VBUF_S)                                                              \
+    __syncthreads();                                                                               \
+    voff ^= VBUF_S;                                                                                \
+    ++rr;                                                                                          \
+  }
 
-    SESSD_SK_LOADP(r0)
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int s = 0; s < RING - 1; ++s) {  // in ring order: the in-loop vmcnt ladder assumes it
-      SESSD_SK_LOADU(s, r0 * NW + s)
+    if constexpr (SPLIT) {
+      SESSD_SS_LOADP(r0)
       __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {  // in ring order
+        SESSD_SS_LOADU(s, r0 * 8 + s)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      SESSD_SS_TRANSFORM(0)
+    } else {
+      SESSD_SK_LOADP(r0)
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int s = 0; s < RING - 1; ++s) {  // in ring order: the in-loop vmcnt ladder assumes it
+        SESSD_SK_LOADU(s, r0 * NW + s)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      SESSD_SK_TRANSFORM(0)
     }
-    SESSD_SK_TRANSFORM(0)
     __syncthreads();
     if (pend_state == 1) {
       // the previous segment's part: its stores are older than the patch loads every thread has just consumed
@@ -361,7 +498,11 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void conv3x3s1_winograd_sk_kernel(
     }
     int voff = 0;
     int rr = r0;
-    while (rr < r1) SESSD_SK_ROUND()
+    if constexpr (SPLIT) {
+      while (rr < r1) SESSD_SS_ROUND()
+    } else {
+      while (rr < r1) SESSD_SK_ROUND()
+    }
 #undef SESSD_SK_LOADP
 #undef SESSD_SK_LOADU
 #undef SESSD_SK_TRANSFORM
@@ -369,6 +510,13 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void conv3x3s1_winograd_sk_kernel(
 #undef SESSD_SK_MMA
 #undef SESSD_SK_STEP
 #undef SESSD_SK_ROUND
+#undef SESSD_SS_LOADP
+#undef SESSD_SS_LOADU
+#undef SESSD_SS_TRANSFORM
+#undef SESSD_SS_READV
+#undef SESSD_SS_MMA
+#undef SESSD_SS_STEP
+#undef SESSD_SS_ROUND
 
     // ---- epilogue: per 32-cout block, M_xi of all 16 xi through LDS, Y = A^T M A per (cout, tile)
     // The arguments only the epilogue needs are re-read from the kernel-argument segment HERE (through an opaque pointer):
@@ -884,7 +1032,7 @@ int launch_rk(const float* in, int batch, int nsets, int cin, int h, int w, cons
   return SESSD_OK;
 }
 
-template <int NW, int CBN>
+template <int NW, int CBN, bool SPLIT = false>
 int launch_sk(const float* in, int batch, int nsets, int cin, int h, int w, const float* upk, float* out, int cout, const float* scale,
               const float* shift, int relu, const float* residual, void* workspace, size_t workspace_bytes, int workgroups,
               hipStream_t stream, const int* tile_list = nullptr, const int* n_list = nullptr, int list_cap = 0, int min_rounds = 1) {
@@ -898,6 +1046,7 @@ int launch_sk(const float* in, int batch, int nsets, int cin, int h, int w, cons
   A.rpu = cin / (2 * NW);
   A.bper = batch / nsets; A.ss_stride = nsets > 1 ? cout : 0;
   A.upk_stride = nsets > 1 ? (long long)sessd_divup(cout, CBN * 32) * (cin >> 1) * (NW * 2 * 32 * 32 / 4) : 0;
+  if (SPLIT && nsets > 1) A.upk_stride = (long long)sessd_divup(cout, CBN * 32) * cin * 3072;  // three bf16 planes: 1.5 x the f32 bytes
   // min_rounds < 0 (list launches only): whole-unit shares, at least -min_rounds units per workgroup
   A.tile_list = tile_list; A.n_list = n_list; A.list_cap = list_cap; A.min_rounds = (min_rounds < 0 && tile_list) ? min_rounds : (min_rounds < 1 ? 1 : min_rounds); A.batch = batch;
   const long long units = (long long)batch * A.tblocks * A.ngroups;
@@ -910,7 +1059,12 @@ int launch_sk(const float* in, int batch, int nsets, int cin, int h, int w, cons
   A.counters = (unsigned*)workspace;
   A.scratch = (float*)((char*)workspace + sessd_align((size_t)units * 4, 256));
   if (tile_list) {   // active-tile mode: the same kernel over a device list of tiles (shares are sized on the device)
-    SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 0, true>), dim3(workgroups), dim3(NW * 64), 0, stream, A);
+    SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 0, true, SPLIT>), dim3(workgroups), dim3(NW * 64), 0, stream, A);
+    SESSD_CHECK_LAUNCH();
+    return SESSD_OK;
+  }
+  if constexpr (SPLIT) {
+    SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 0, false, true>), dim3(workgroups), dim3(NW * 64), 0, stream, A);
     SESSD_CHECK_LAUNCH();
     return SESSD_OK;
   }
@@ -938,10 +1092,11 @@ int default_workgroups(int shape, int* out) {
 extern "C" {
 
 // Scratch + counters of sessd_conv3x3_winograd_sk. shape 0: 8 waves x 128 couts per workgroup (one per CU), shape 1: 4 waves x
-// 64 couts (two per CU); workgroups 0 = that default. The caller zeroes the workspace ONCE (the kernel leaves the counters
-// zero) and must not share it between launches that may run concurrently.
+// 64 couts (two per CU), shape 2: 4 waves x 128 couts, shape 3: shape 0 on the bf16 matrix cores (three-way split);
+// workgroups 0 = that default. The caller zeroes the workspace ONCE (the kernel leaves the counters zero) and must not share
+// it between launches that may run concurrently.
 size_t sessd_conv3x3_winograd_sk_workspace_bytes(int batch, int h, int w, int cout, int shape, int workgroups) {
-  if (batch < 1 || h < 2 || w < 2 || cout < 1 || workgroups < 0 || shape < 0 || shape > 2) return 0;
+  if (batch < 1 || h < 2 || w < 2 || cout < 1 || workgroups < 0 || shape < 0 || shape > 3) return 0;
   if (workgroups == 0 && default_workgroups(shape, &workgroups) != SESSD_OK) return 0;
   const int cpu = shape == 1 ? 64 : 128;
   const size_t units = (size_t)batch * sessd_divup((h / 2) * (w / 2), 32) * sessd_divup(cout, cpu);
@@ -951,7 +1106,8 @@ size_t sessd_conv3x3_winograd_sk_workspace_bytes(int batch, int h, int w, int co
 // Conv2d(cin, cout, 3, stride 1, padding 1) + folded BatchNorm + ReLU + residual, fused Winograd F(2x2,3x3), stream-K over
 // `workgroups` persistent workgroups (a multiple of 8; 0 = the shape's default).
 // upk = U = G g G^T packed [ceil(cout / C)][cin/2][NW][2][32][C/32][16/NW] with (NW, C) = (8, 128) for shape 0, (4, 64) for
-// shape 1 (ops.pack_winograd_sk); even H, W; cin % (2 NW) == 0.
+// shape 1; shape 3: three bf16 planes [ceil(cout / 128)][wave 8][cin/2 steps][3][64][8] (ops.pack_winograd_sk); even H, W;
+// cin % (2 NW) == 0.
 // Several layers of ONE shape in one launch (conv_0 / conv_1 of the SSFA neck, rpn_v1.py:201-210): the batch dimension is
 // nsets consecutive groups of batch / nsets elements, group s convolved with weight set s -- upk = nsets packings back to back,
 // scale / shift = nsets x cout. One round list, one pipeline fill and one tail instead of nsets.
@@ -959,7 +1115,7 @@ int sessd_conv3x3_winograd_sk_sets(const float* in, int batch, int nsets, int ci
                                    int cout, const float* scale, const float* shift, int relu, const float* residual,
                                    void* workspace, size_t workspace_bytes, int shape, int workgroups, hipStream_t stream) {
   if ((h & 1) || (w & 1) || batch < 1 || nsets < 1 || batch % nsets || cout < 1 || workgroups < 0 || (workgroups & 7) || shape < 0 ||
-      shape > 2)
+      shape > 3)
     return SESSD_EINVAL;
   if (workgroups == 0) {
     const int rc = default_workgroups(shape, &workgroups);
@@ -969,6 +1125,8 @@ int sessd_conv3x3_winograd_sk_sets(const float* in, int batch, int nsets, int ci
     return launch_rk(in, batch, nsets, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace, workspace_bytes, workgroups, stream);
   if (shape == 1)
     return launch_sk<4, 2>(in, batch, nsets, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace, workspace_bytes, workgroups, stream);
+  if (shape == 3)
+    return launch_sk<8, 4, true>(in, batch, nsets, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace, workspace_bytes, workgroups, stream);
   return launch_sk<8, 4>(in, batch, nsets, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace, workspace_bytes, workgroups, stream);
 }
 
@@ -982,8 +1140,8 @@ int sessd_conv3x3_winograd_sk_active(const float* in, int batch, int cin, int h,
                                      const float* scale, const float* shift, int relu, const float* residual,
                                      const int32_t* tile_list, const int32_t* n_list, int list_cap, int min_rounds, void* workspace,
                                      size_t workspace_bytes, int shape, int workgroups, hipStream_t stream) {
-  if ((h & 1) || (w & 1) || batch < 1 || cout < 1 || workgroups < 0 || (workgroups & 7) || shape < 0 || shape > 1 || !tile_list ||
-      !n_list || list_cap < 1)
+  if ((h & 1) || (w & 1) || batch < 1 || cout < 1 || workgroups < 0 || (workgroups & 7) || shape < 0 || shape > 3 || shape == 2 ||
+      !tile_list || !n_list || list_cap < 1)
     return SESSD_EINVAL;
   if (workgroups == 0) {
     const int rc = default_workgroups(shape, &workgroups);
@@ -992,6 +1150,9 @@ int sessd_conv3x3_winograd_sk_active(const float* in, int batch, int cin, int h,
   if (shape == 1)
     return launch_sk<4, 2>(in, batch, 1, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace, workspace_bytes, workgroups,
                            stream, tile_list, n_list, list_cap, min_rounds);
+  if (shape == 3)
+    return launch_sk<8, 4, true>(in, batch, 1, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace, workspace_bytes,
+                                 workgroups, stream, tile_list, n_list, list_cap, min_rounds);
   return launch_sk<8, 4>(in, batch, 1, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace, workspace_bytes, workgroups,
                          stream, tile_list, n_list, list_cap, min_rounds);
 }

@@ -10,6 +10,7 @@ it reads their parameters (reference state_dict layout), folds eval-mode BatchNo
 (scale, shift) and packs the weights into the MFMA fragment layouts of the kernels.
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -32,6 +33,11 @@ def fold_bn(bn):
 
 
 # (kind, cin, cout, ksize, stride, padding, indice_key) -- det3d/models/backbones/scn.py:106-148
+# Stream-K Winograd shape 3 (8 waves x 128 couts on the bf16 matrix cores, f32 operands split three ways; csrc/dense_wino_sk.hip)
+# among the autotune's candidates and in the default list configuration. SESSD_WINO_SPLIT=0 leaves it out (A/B runs in one tree).
+WINO_SPLIT = os.environ.get("SESSD_WINO_SPLIT", "1") != "0"
+WINO_LIST_SHAPES = (0, 1, 3) if WINO_SPLIT else (0, 1)
+
 SPMIDDLE_LAYERS = [
     ("subm", 4, 16, 3, 1, 0, "subm0"), ("subm", 16, 16, 3, 1, 0, "subm0"),
     ("conv", 16, 32, 3, 2, 1, None),
@@ -534,6 +540,8 @@ class InferenceEngine:
         self.sk_ws = torch.zeros_like(other.sk_ws) if other.sk_ws is not None else None
 
     DEFAULT_ACTIVE_CFG = {0: (1, 4), 1: (0, 1), 2: (1, 2), 3: (30, 4), 4: (1, 2), 5: (0, 1), 6: (11, 0), 7: (30, 8), 8: (4, 0), 9: (0, 8)}
+    if WINO_SPLIT:   # the 8-wave list layers on the bf16 matrix cores (shape 3)
+        DEFAULT_ACTIVE_CFG = {l: ((3, mr) if shape == 0 else (shape, mr)) for l, (shape, mr) in DEFAULT_ACTIVE_CFG.items()}
 
     def force_active_tiles(self, active_cfg=None):
         """The configuration autotune() ends in on MI355X, WITHOUT timing anything: the neck's 3x3 stride-1 layers on the stream-K
@@ -549,7 +557,15 @@ class InferenceEngine:
                    [int(lib.sessd_conv2d_sk_workspace_bytes(B, self.H, self.W, 256, 1, 0))])
         if self.sk_ws is None or self.sk_ws.numel() < need:
             self.sk_ws = torch.zeros(need, dtype=torch.uint8, device=self.dev)
-        self.active_cfg = dict(self.DEFAULT_ACTIVE_CFG if active_cfg is None else active_cfg)
+        cfg = dict(self.DEFAULT_ACTIVE_CFG if active_cfg is None else active_cfg)
+        for l, (shape, mr) in cfg.items():
+            # a Winograd list layer needs its packing for the chosen shape (a missing one is an error, not a fall-back)
+            if l in self.ACTIVE_SK or l == self.ACTIVE_PAIR:
+                continue
+            layers = self.ACTIVE_SLOTS[l][1] if l == self.ACTIVE_CONV else (self.ACTIVE_SLOTS[l][1],)
+            if any(pc.upk_sk(shape) is None for pc, _, _ in layers):
+                raise ValueError("active-tile layer %s: no stream-K Winograd packing for shape %d" % (self.ACTIVE_SLOTS[l][0], shape))
+        self.active_cfg = cfg
         return self.active_cfg
 
     def autotune(self, candidates=(1, 2, 3, 4, 6, 11, 12), reps=5):
@@ -613,7 +629,7 @@ class InferenceEngine:
                     # couts / 4 waves x 64 couts. One workspace per engine: its launches are serialised on the engine's stream.
                     # (tile_cfg 24, the third generation with the output transform in registers, is selectable but not a candidate:
                     # measured 81 / 96 us against 63 / 66 us for 22 / 23 on the two SSFA shapes, profiles/r4_wino_rk_probe.json)
-                    for cfg, shape in ((22, 0), (23, 1)) if self.allow_streamk else ():
+                    for cfg, shape in ((22, 0), (23, 1)) + (((25, 3),) if WINO_SPLIT else ()) if self.allow_streamk else ():
                         if pc.upk_sk(shape) is not None:
                             need = int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(x.shape[0], x.shape[2], x.shape[3], pc.cout, shape, 0))
                             if self.sk_ws is None or self.sk_ws.numel() < need:
@@ -706,13 +722,13 @@ class InferenceEngine:
                 # the two layers' own launches
                 (p0, s0, t0_), (p1, s1, t1_) = layer
                 c01 = self.tile_cfg.get("conv_0")
-                if self.merge_branch_convs and c01 in (22, 23, 24) and self.tile_cfg.get("conv_1") == c01 and self._branch_sets(c01 - 22) is not None:
+                if self.merge_branch_convs and c01 in (22, 23, 24, 25) and self.tile_cfg.get("conv_1") == c01 and self._branch_sets(c01 - 22) is not None:
                     sets = self._branch_sets(c01 - 22)
                     dense_t = timed(lambda: ops.conv2d_winograd_sk_sets(t["mid"], sets["upk"], 2, 128, sets["scale"], sets["shift"], True, t["o"],
                                                                         c01 - 22, self.sk_ws, self._wgs(c01 - 22)))
                 else:
                     dense_t = self.tune_report.get("conv_0", (None, 0.0))[1] + self.tune_report.get("conv_1", (None, 0.0))[1]
-                for shape in (0, 1):
+                for shape in WINO_LIST_SHAPES:
                     if p0.upk_sk(shape) is None or p1.upk_sk(shape) is None:
                         continue
                     need = int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(self.B, self.H, self.W, p0.cout, shape, 0))
@@ -749,7 +765,7 @@ class InferenceEngine:
                         if tt < best[1]:
                             best = ((30, mr), tt)
             else:
-                for shape in (0, 1):
+                for shape in WINO_LIST_SHAPES:
                     if pc.upk_sk(shape) is None:
                         continue
                     need = int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(self.B, x_in.shape[2], x_in.shape[3], pc.cout, shape, 0))
@@ -989,7 +1005,7 @@ class InferenceEngine:
                 e1.record()
                 self._kmarks.append(("conv_0+conv_1", e0, e1))
             o0, o1 = t["o0"], t["o1"]
-        elif self.merge_branch_convs and c01 in (22, 23, 24) and self.tile_cfg.get("conv_1") == c01 and self._tuning is None \
+        elif self.merge_branch_convs and c01 in (22, 23, 24, 25) and self.tile_cfg.get("conv_1") == c01 and self._tuning is None \
                 and self.sk_ws is not None and self._branch_sets(c01 - 22) is not None:
             sets = self._branch_sets(c01 - 22)
             if self._kmarks is not None:

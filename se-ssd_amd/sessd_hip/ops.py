@@ -694,7 +694,7 @@ def _repack_table(kind, jobs):
             if j["kind"] == 0:
                 total = (j["cin"] // 2) * len(j["taps"]) * 2 * cp
             else:
-                cpad = cp if j["layout"] == 0 else ((j["cout"] + 127) // 128 * 128 if j["layout"] == 1 else (j["cout"] + 63) // 64 * 64)
+                cpad = cp if j["layout"] == 0 else ((j["cout"] + 127) // 128 * 128 if j["layout"] in (1, 4) else (j["cout"] + 63) // 64 * 64)
                 total = cpad * j["cin"]
         else:
             a.kv, a.cin, a.cout, a.adjoint, a.reverse_k = j["kv"], j["cin"], j["cout"], j["adjoint"], j["reverse_k"]
@@ -1286,7 +1286,7 @@ class PackedConv:
         self.cin, self.cout, self.kind, self.stride = cin, cout, kind, stride
         self._w3 = None      # (weight, adjoint): the 3x3 stride-1 weight the Winograd packings are made from, on demand
         self._upk = None
-        self._upk_sk = [None, None, None]
+        self._upk_sk = [None, None, None, None]
         self._sk = None      # argument block of sessd_conv2d_sk (tile_cfg 30), made when first asked for
         self._registry = None  # RepackRegistry that keeps this object fresh (training step), else None
 
@@ -1299,8 +1299,8 @@ class PackedConv:
         return self._upk
 
     def upk_sk(self, shape):
-        """U packed for sessd_conv3x3_winograd_sk (tile_cfg 22 / 23 / 24 = shape 0 / 1 / 2); None if not eligible."""
-        if self._upk_sk[shape] is None and self._w3 is not None and self.cin % (16, 8, 16)[shape] == 0:
+        """U packed for sessd_conv3x3_winograd_sk (tile_cfg 22 / 23 / 24 / 25 = shape 0 / 1 / 2 / 3); None if not eligible."""
+        if self._upk_sk[shape] is None and self._w3 is not None and self.cin % (16, 8, 16, 16)[shape] == 0:
             make = lambda: pack_winograd_sk(self._w3[0], shape, adjoint=self._w3[1])
             self._upk_sk[shape] = self._registry.create(make) if self._registry is not None else make()
         return self._upk_sk[shape]
@@ -1400,6 +1400,8 @@ def _winograd_pack(weight, layout, adjoint):
         out = torch.empty((ci // 2, 4, 2, (co + 31) // 32 * 32, 4), dtype=torch.float32, device=w.device)
     elif layout == 3:   # shape 2 (register-resident output transform): [cout group of 128][k-step][wave 4][parity][cout % 32][xi 16]
         out = torch.empty(((co + 127) // 128, ci // 2, 4, 2, 32, 16), dtype=torch.float32, device=w.device)
+    elif layout == 4:   # shape 3 (bf16 matrix cores): three bf16 planes [cout group of 128][wave 8][step][plane 3][lane 64][8 channels]
+        out = torch.empty(((co + 127) // 128, 8, ci // 2, 3, 64, 8), dtype=torch.bfloat16, device=w.device)
     else:
         nw, c = ((8, 128), (4, 64))[layout - 1]
         out = torch.empty(((co + c - 1) // c, ci // 2, nw, 2, 32, c // 32, 16 // nw), dtype=torch.float32, device=w.device)
@@ -1423,7 +1425,9 @@ def winograd_u(weight):
 def pack_winograd_sk(weight, shape=0, adjoint=False):
     """U for sessd_conv3x3_winograd_sk: [ceil(Cout/C)][Cin/2][wave NW][channel parity 2][cout%32][(cout/32)%(C/32)][xi%(16/NW)]
     with xi = (16/NW) * wave + xi%(16/NW) and (NW, C) = (8, 128) for shape 0, (4, 64) for shape 1 -- the 8 A operands of a lane
-    and k-step are 32 contiguous bytes. One launch (sessd_conv3x3_winograd_pack)."""
+    and k-step are 32 contiguous bytes. Shape 3: U split into three bfloat16 planes (u = u0 + u1 + u2 exactly), [ceil(Cout/128)]
+    [wave 8][step = (cin/16) * 8 + xi%2 * 4 + (cout/32)%4][plane 3][lane = (cin/8)%2 * 32 + cout%32][cin%8], xi = 2 wave + xi%2.
+    One launch (sessd_conv3x3_winograd_pack)."""
     return _winograd_pack(weight, 1 + shape, adjoint)
 
 
@@ -1677,11 +1681,12 @@ def conv2d(x, pc, scale=None, shift=None, relu=True, residual=None, out=None, ti
         th, tw = H, W
     if out is None:
         out = torch.empty((B, pc.cout, Ho, Wo), dtype=torch.float32, device=x.device)
-    if tile_cfg in (22, 23, 24):
+    if tile_cfg in (22, 23, 24, 25):
         shape = tile_cfg - 22
         upk = pc.upk_sk(shape) if pc.kind == "conv" else None
         if upk is None or (H & 1) or (W & 1):
-            raise ValueError("tile_cfg 22/23/24 (stream-K Winograd) needs a 3x3 stride-1 conv with cin % 16 (22, 24) / 8 (23) == 0 and even H, W")
+            raise ValueError("tile_cfg 22/23/24/25 (stream-K Winograd) needs a 3x3 stride-1 conv with cin % 16 (22, 24, 25) / 8 (23) == 0 "
+                             "and even H, W")
         if workspace is None:
             key = (x.device.index, _cache_scope(), shape, workgroups)
             need = int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(B, H, W, pc.cout, shape, workgroups))

@@ -656,6 +656,18 @@ int sessd_ssfa_fuse_head_keys(const float* x0, const float* x1, const float* w0,
                               float* out, const float* head_w, const float* head_b, int nout, float* head_out,
                               float score_thresh, unsigned long long* keys, int key_cap, int32_t* key_count,
                               sessd_stream_t stream);
+/* The multi-task form (mg_head_sessd.py:477-481: one Head per task): head_w (num_tasks * 22, channels) = per task the
+ * concatenated conv_box | conv_cls | conv_dir | conv_iou weights, head_b (num_tasks * 22) or NULL, head_out
+ * (B, num_tasks, 22, num_pixels) planar = (B, num_tasks * 22, num_pixels); 1 <= num_tasks <= 4, one class and two rotations per
+ * task. The maps are read and blended once per pixel, the heads run one after the other: task t's planes are bit for bit those
+ * of sessd_ssfa_fuse_head_keys with task t's weights. keys (B * num_tasks, key_cap) / key_count (B * num_tasks, zeroed by the
+ * caller): the score-filter keys per (frame, task), anchor id local to the task; input of sessd_predict_tasks. keys == NULL:
+ * no score filter. num_tasks == 1 is sessd_ssfa_fuse_head_keys. */
+int sessd_ssfa_fuse_head_tasks(const float* x0, const float* x1, const float* w0, const float* w1, float bn_scale0,
+                               float bn_shift0, float bn_scale1, float bn_shift1, int batch, int channels, int num_pixels,
+                               float* out, const float* head_w, const float* head_b, int num_tasks, float* head_out,
+                               float score_thresh, unsigned long long* keys, int key_cap, int32_t* key_count,
+                               sessd_stream_t stream);
 
 /* ------------------------------------------------------------------ predict / post-processing (a11-a14)
  * replaces det3d/models/bbox_heads/mg_head_sessd.py:893-1057 (MultiGroupHead.predict / get_task_detections),
@@ -680,6 +692,23 @@ int sessd_predict_fused(const float* head, int batch, int num_pixels, const floa
                         float* out_score, int32_t* out_label, int32_t* out_count, const unsigned long long* ext_keys,
                         const int32_t* ext_key_count, float* records, int32_t* record_counts, int capacity_frames,
                         int32_t* cursor, void* workspace, size_t workspace_bytes, sessd_stream_t stream);
+/* Multi-task predict (mg_head_sessd.py:893-943: get_task_detections per task with its own anchors, concatenated in task order,
+ * label = task index): head (B, num_tasks, 22, H*W) planar, 1 <= num_tasks <= 4, one class and two rotations per task; anchors
+ * (num_tasks, A, 7) shared by all frames (anchors_per_frame = 0) or (B, num_tasks, A, 7) (anchors_per_frame = A), A = 2*H*W;
+ * frustum (B,1,6,4,3) per frame or NULL. Every task applies score_thresh, pre_max_size, the NMS and post_max_size on its own.
+ * Outputs: out_box (B, num_tasks*post, 7), out_score / out_label (B, num_tasks*post), out_count (B,): rows [0, out_count[b]) =
+ * task 0's detections in NMS order, then task 1's, ...; out_task_count (B, num_tasks) or NULL = rows per task. ext_keys
+ * (B*num_tasks, 2*H*W) / ext_key_count (B*num_tasks) from sessd_ssfa_fuse_head_tasks; records (capacity_frames,
+ * num_tasks*post, 9) with the ring rule of sessd_pack_detections (*cursor += batch). num_tasks == 1 is sessd_predict_fused (same
+ * launches, same workspace); num_tasks > 1 adds one small merge launch. */
+size_t sessd_predict_tasks_workspace_bytes(int batch, int num_tasks, int num_anchors, int pre_max_size, int post_max_size);
+int sessd_predict_tasks(const float* head, int batch, int num_tasks, int num_pixels, const float* anchors,
+                        int anchors_per_frame, const double* frustum, float score_thresh, int pre_max_size, int post_max_size,
+                        float nms_iou_thresh, const float* post_center_range6, float direction_offset, float* out_box,
+                        float* out_score, int32_t* out_label, int32_t* out_count, int32_t* out_task_count,
+                        const unsigned long long* ext_keys, const int32_t* ext_key_count, float* records,
+                        int32_t* record_counts, int capacity_frames, int32_t* cursor, void* workspace, size_t workspace_bytes,
+                        sessd_stream_t stream);
 /* spconv.utils.rbbox_iou / rbbox_intersection (third-party spconv v1, imported by det3d/core/bbox/box_np_ops.py:9 for riou_cc /
  * rinter_cc :20-50): pairwise IoU (mode 0) or intersection area (mode 1) of convex quads given as corners (n,4,2) x (k,4,2);
  * pairs whose caller-supplied stand-up IoU is <= standup_thresh stay 0. standup_iou and out are (n,k) row-major. */

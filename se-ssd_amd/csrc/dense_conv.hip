@@ -657,23 +657,29 @@ __global__ __launch_bounds__(256) void ssfa_fuse_kernel(const float* __restrict_
 // register, so the SSFA output (18 MB per frame) is neither written nor read back and one launch disappears. Thread = (pixel,
 // channel quarter) as above; the head weights sit in LDS (all lanes of a wave read the same address: broadcast); the four
 // quarter sums of a (pixel, head channel) meet in LDS and are added in quarter order. `out` may be null (inference).
-template <int NOUT, int CPER>
+// MULTI (mg_head_sessd.py:477-481, one Head per task): ntask heads of NOUT channels each, hw (ntask * NOUT, C), hout planar
+// (B, ntask, NOUT, npix), keys / key_count per (frame, task). The maps are fetched and blended ONCE per pixel (the blend
+// replaces v0 in registers); the heads then run one after the other through the SAME NOUT-channel LDS staging (ntask * NOUT
+// channels of weights and quarter sums would be ~100 KB and cost the second workgroup per CU), each with the fma order and the
+// quarter-order sum of the single-task form: task t's planes carry the bits of a single-task launch with task t's weights.
+template <int NOUT, int CPER, bool MULTI>
 __global__ __launch_bounds__(256, 2) void ssfa_fuse_head_kernel(const float* __restrict__ x0, const float* __restrict__ x1,
                                                               const float* __restrict__ w0, const float* __restrict__ w1,
                                                               float s0, float t0, float s1, float t1, int npix,
                                                               float* __restrict__ out, const float* __restrict__ hw,
                                                               const float* __restrict__ hb, float* __restrict__ hout,
                                                               float score_thresh, unsigned long long* __restrict__ keys,
-                                                              int key_cap, int* __restrict__ key_count) {
+                                                              int key_cap, int* __restrict__ key_count, int num_tasks) {
   constexpr int C = 4 * CPER;
   __shared__ float part[2][4][64];
-  __shared__ __attribute__((aligned(16))) float s_hw[NOUT * C];  // head weights
+  __shared__ __attribute__((aligned(16))) float s_hw[NOUT * C];  // head weights (of one task at a time)
   __shared__ float s_acc[4 * NOUT * 64];                          // quarter sums of the head channels
   const int px = threadIdx.x & 63, cq = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int p = blockIdx.x * 64 + px;
   const int b = blockIdx.y;
   const int c0 = cq * CPER;
   const bool live = p < npix;
+  const int ntask = MULTI ? num_tasks : 1;
   // buffer resources over this batch element's maps: lane offset = pixel, SGPR offset = channel plane (no 64-bit address per
   // channel in VGPRs); a dead lane reads / writes out of range
   const unsigned plane4 = (unsigned)npix * 4u, mbytes = (unsigned)C * plane4;
@@ -706,52 +712,71 @@ __global__ __launch_bounds__(256, 2) void ssfa_fuse_head_kernel(const float* __r
   const float e0 = expf(a0 - m), e1 = expf(a1 - m);
   const float inv = 1.f / (e0 + e1);
   const float p0 = e0 * inv, p1 = e1 * inv;
-  float acc[NOUT];
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) acc[o] = 0.f;
-#pragma unroll
-  for (int c = 0; c < CPER; c += 4) {
-    float bl[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      bl[e] = v0[c + e] * p0 + v1[c + e] * p1;
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, bl[e]), ro, (int)vp, (int)((unsigned)(c0 + c + e) * plane4), 0);
-    }
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o) {
-      const float4 w = *reinterpret_cast<const float4*>(s_hw + o * C + c0 + c);
-      acc[o] = fmaf(bl[0], w.x, acc[o]);
-      acc[o] = fmaf(bl[1], w.y, acc[o]);
-      acc[o] = fmaf(bl[2], w.z, acc[o]);
-      acc[o] = fmaf(bl[3], w.w, acc[o]);
-    }
-    __builtin_amdgcn_sched_barrier(0);  // fully unrolled, hipcc would hoist all 8 x NOUT weight reads: 700 registers
-  }
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) s_acc[(cq * NOUT + o) * 64 + px] = acc[o];
-  __syncthreads();
-  if (!live) return;
-  auto head_value = [&](int o) {  // quarter sums in quarter order + bias: the value stored for (pixel, head channel o)
-    const float v = ((s_acc[(0 * NOUT + o) * 64 + px] + s_acc[(1 * NOUT + o) * 64 + px]) + s_acc[(2 * NOUT + o) * 64 + px]) +
-                    s_acc[(3 * NOUT + o) * 64 + px];
-    return v + (hb ? hb[o] : 0.f);
+  auto blend_store = [&](int c) {  // the SSFA output of channel c0 + c: computed (and written, when asked for) once per pixel
+    const float v = v0[c] * p0 + v1[c] * p1;
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ro, (int)vp, (int)((unsigned)(c0 + c) * plane4), 0);
+    return v;
   };
-  for (int o = cq; o < NOUT; o += 4) hout[((size_t)b * NOUT + o) * npix + p] = head_value(o);
-  // The score filter of MultiGroupHead.predict (mg_head_sessd.py:956-972; postprocess.hip: score_filter_kernel) while the
-  // logits are at hand: sigmoid(cls) >= thresh -> key (~rectified score | anchor id) appended to the frame's candidate list.
-  // Planar head layout [box 14 | cls 2 | dir 4 | iou 2], two anchors per location; the same float operations on the same
-  // values as the stand-alone kernel reads back from `hout`, so the keys are the same set.
-  if (keys && cq == 0) {
+  if constexpr (MULTI) {
 #pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      const float sg = 1.0f / (1.0f + expf(-head_value(14 + a)));
-      if (sg >= score_thresh) {
-        const float r = (head_value(20 + a) + 1.0f) * 0.5f;
-        const float sc = sg * (r * r * r * r);
-        const unsigned aid = (unsigned)(p * 2 + a);
-        const unsigned long long key = ((unsigned long long)(~__float_as_uint(sc)) << 32) | aid;
-        const int slot = atomicAdd(&key_count[b], 1);
-        if (slot < key_cap) keys[(size_t)b * key_cap + slot] = key;
+    for (int c = 0; c < CPER; ++c) v0[c] = blend_store(c);
+  }
+#pragma unroll 1
+  for (int t = 0; t < ntask; ++t) {
+    if (MULTI && t > 0) {  // every thread is done with the previous task's weights and quarter sums
+      __syncthreads();
+      for (int k = threadIdx.x; k < NOUT * C; k += 256) s_hw[k] = hw[(size_t)t * NOUT * C + k];
+      __syncthreads();
+    }
+    float acc[NOUT];
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o) acc[o] = 0.f;
+#pragma unroll
+    for (int c = 0; c < CPER; c += 4) {
+      float bl[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if constexpr (MULTI) bl[e] = v0[c + e];
+        else bl[e] = blend_store(c + e);
+      }
+#pragma unroll
+      for (int o = 0; o < NOUT; ++o) {
+        const float4 w = *reinterpret_cast<const float4*>(s_hw + o * C + c0 + c);
+        acc[o] = fmaf(bl[0], w.x, acc[o]);
+        acc[o] = fmaf(bl[1], w.y, acc[o]);
+        acc[o] = fmaf(bl[2], w.z, acc[o]);
+        acc[o] = fmaf(bl[3], w.w, acc[o]);
+      }
+      __builtin_amdgcn_sched_barrier(0);  // fully unrolled, hipcc would hoist all 8 x NOUT weight reads: 700 registers
+    }
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o) s_acc[(cq * NOUT + o) * 64 + px] = acc[o];
+    __syncthreads();
+    if (!live) continue;  // dead lanes still meet the barriers of the next task
+    const int v = b * ntask + t;  // (frame, task): plane block of `hout`, key list
+    const float* hbt = hb ? hb + t * NOUT : nullptr;
+    auto head_value = [&](int o) {  // quarter sums in quarter order + bias: the value stored for (pixel, head channel o)
+      const float s = ((s_acc[(0 * NOUT + o) * 64 + px] + s_acc[(1 * NOUT + o) * 64 + px]) + s_acc[(2 * NOUT + o) * 64 + px]) +
+                      s_acc[(3 * NOUT + o) * 64 + px];
+      return s + (hbt ? hbt[o] : 0.f);
+    };
+    for (int o = cq; o < NOUT; o += 4) hout[((size_t)v * NOUT + o) * npix + p] = head_value(o);
+    // The score filter of MultiGroupHead.predict (mg_head_sessd.py:956-972; postprocess.hip: score_filter_kernel) while the
+    // logits are at hand: sigmoid(cls) >= thresh -> key (~rectified score | anchor id) appended to the (frame, task)'s candidate
+    // list. Planar head layout [box 14 | cls 2 | dir 4 | iou 2], two anchors per location; the same float operations on the
+    // same values as the stand-alone kernel reads back from `hout`, so the keys are the same set.
+    if (keys && cq == 0) {
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        const float sg = 1.0f / (1.0f + expf(-head_value(14 + a)));
+        if (sg >= score_thresh) {
+          const float r = (head_value(20 + a) + 1.0f) * 0.5f;
+          const float sc = sg * (r * r * r * r);
+          const unsigned aid = (unsigned)(p * 2 + a);
+          const unsigned long long key = ((unsigned long long)(~__float_as_uint(sc)) << 32) | aid;
+          const int slot = atomicAdd(&key_count[v], 1);
+          if (slot < key_cap) keys[(size_t)v * key_cap + slot] = key;
+        }
       }
     }
   }
@@ -1197,29 +1222,47 @@ int sessd_ssfa_fuse(const float* x0, const float* x1, const float* w0, const flo
 }
 
 
-// rpn_v1.py:227-233 + mg_head_sessd.py:217-230 in one launch: the SSFA fusion tail with the four 1x1 heads applied to its result
-// while it is in registers. head_w (nout, channels) row-major = the concatenated conv weights, head_b (nout) or null,
-// head_out (B, nout, num_pixels) planar. out (B, C, num_pixels) receives the SSFA output when not null. nout == 22 (the
-// single-task car head: 14 box + 2 cls + 4 dir + 2 iou), channels 128 (the SSFA neck) or 64.
+// rpn_v1.py:227-233 + mg_head_sessd.py:217-230 in one launch: the SSFA fusion tail with the 1x1 heads of `num_tasks` tasks
+// (mg_head_sessd.py:477-481) applied to its result while it is in registers. head_w (num_tasks * 22, channels) row-major = per
+// task the concatenated conv weights [box 14 | cls 2 | dir 4 | iou 2], head_b (num_tasks * 22) or null, head_out
+// (B, num_tasks, 22, num_pixels) planar = (B, num_tasks * 22, num_pixels). out (B, C, num_pixels) receives the SSFA output when
+// not null. 1 <= num_tasks <= 4, channels 128 (the SSFA neck) or 64. Task t's planes are bit for bit those of a single-task
+// launch with task t's weights.
 // keys != NULL: the launch also runs the score filter of predict (score_thresh on sigmoid(cls), IoU-rectified score) and
-// appends the candidates' 64-bit keys (~score bits << 32 | anchor id, anchor id = 2 * pixel + a) to keys[b * key_cap ..] with
-// key_count[b] (zeroed by the caller) counting them -- what sessd_predict_fused takes as ext_keys / ext_key_count.
+// appends the candidates' 64-bit keys (~score bits << 32 | anchor id, anchor id = 2 * pixel + a, local to the task) to
+// keys[(b * num_tasks + t) * key_cap ..] with key_count[b * num_tasks + t] (zeroed by the caller) counting them -- what
+// sessd_predict_tasks takes as ext_keys / ext_key_count.
+int sessd_ssfa_fuse_head_tasks(const float* x0, const float* x1, const float* w0, const float* w1, float bn_scale0, float bn_shift0,
+                               float bn_scale1, float bn_shift1, int batch, int channels, int num_pixels, float* out,
+                               const float* head_w, const float* head_b, int num_tasks, float* head_out, float score_thresh,
+                               unsigned long long* keys, int key_cap, int* key_count, hipStream_t stream) {
+  if (batch < 1 || (channels != 128 && channels != 64) || num_pixels < 1 || num_tasks < 1 || num_tasks > 4) return SESSD_EINVAL;
+  if ((long long)channels * num_pixels * 4 >= 0x7fffffffLL) return SESSD_EINVAL;  // 32-bit buffer offsets per batch element
+  if ((keys == nullptr) != (key_count == nullptr) || (keys && key_cap < 1)) return SESSD_EINVAL;
+  const dim3 grid(sessd_divup(num_pixels, 64), batch);
+#define SESSD_FUSE_HEAD(CPER, MULTI)                                                                                            \
+  SESSD_LAUNCH((ssfa_fuse_head_kernel<22, CPER, MULTI>), grid, dim3(256), 0, stream, x0, x1, w0, w1, bn_scale0, bn_shift0,     \
+               bn_scale1, bn_shift1, num_pixels, out, head_w, head_b, head_out, score_thresh, keys, key_cap, key_count, num_tasks)
+  if (channels == 128) {
+    if (num_tasks == 1) SESSD_FUSE_HEAD(32, false);
+    else SESSD_FUSE_HEAD(32, true);
+  } else {
+    if (num_tasks == 1) SESSD_FUSE_HEAD(16, false);
+    else SESSD_FUSE_HEAD(16, true);
+  }
+#undef SESSD_FUSE_HEAD
+  SESSD_CHECK_LAUNCH();
+  return SESSD_OK;
+}
+
+// the single-task forms: nout == 22 (the car head: 14 box + 2 cls + 4 dir + 2 iou)
 int sessd_ssfa_fuse_head_keys(const float* x0, const float* x1, const float* w0, const float* w1, float bn_scale0, float bn_shift0,
                               float bn_scale1, float bn_shift1, int batch, int channels, int num_pixels, float* out,
                               const float* head_w, const float* head_b, int nout, float* head_out, float score_thresh,
                               unsigned long long* keys, int key_cap, int* key_count, hipStream_t stream) {
-  if (batch < 1 || (channels != 128 && channels != 64) || num_pixels < 1 || nout != 22) return SESSD_EINVAL;
-  if ((long long)channels * num_pixels * 4 >= 0x7fffffffLL) return SESSD_EINVAL;  // 32-bit buffer offsets per batch element
-  if ((keys == nullptr) != (key_count == nullptr) || (keys && key_cap < 1)) return SESSD_EINVAL;
-  const dim3 grid(sessd_divup(num_pixels, 64), batch);
-  if (channels == 128)
-    SESSD_LAUNCH((ssfa_fuse_head_kernel<22, 32>), grid, dim3(256), 0, stream, x0, x1, w0, w1, bn_scale0, bn_shift0, bn_scale1,
-                 bn_shift1, num_pixels, out, head_w, head_b, head_out, score_thresh, keys, key_cap, key_count);
-  else
-    SESSD_LAUNCH((ssfa_fuse_head_kernel<22, 16>), grid, dim3(256), 0, stream, x0, x1, w0, w1, bn_scale0, bn_shift0, bn_scale1,
-                 bn_shift1, num_pixels, out, head_w, head_b, head_out, score_thresh, keys, key_cap, key_count);
-  SESSD_CHECK_LAUNCH();
-  return SESSD_OK;
+  if (nout != 22) return SESSD_EINVAL;
+  return sessd_ssfa_fuse_head_tasks(x0, x1, w0, w1, bn_scale0, bn_shift0, bn_scale1, bn_shift1, batch, channels, num_pixels, out,
+                                    head_w, head_b, 1, head_out, score_thresh, keys, key_cap, key_count, stream);
 }
 
 int sessd_ssfa_fuse_head(const float* x0, const float* x1, const float* w0, const float* w1, float bn_scale0, float bn_shift0,

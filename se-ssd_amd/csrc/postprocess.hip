@@ -19,6 +19,11 @@
 // with the head and the frame has one launch and one 35 k-thread pass less.
 // Head tensor layout consumed here: planar (B, 22, H*W): ch 0..13 box codes (anchor-major, 7 each),
 // 14..15 cls, 16..19 dir (2 per anchor), 20..21 iou; anchor id = pixel*2 + a (mg_head_sessd.py:409-481).
+// Multi-task heads (mg_head_sessd.py:893-943: get_task_detections once per task with its own anchors, then concatenation in
+// task order with label offsets): (frame b, task t) runs through K1-K5 as the virtual frame v = b * T + t -- the head tensor
+// (B, T, 22, H*W), keys, candidates and masks are all indexed by a frame with fixed strides -- into per-task rows of the
+// workspace, and one small launch (merge_tasks_kernel) concatenates them per real frame and writes the record. T = 1 has no
+// such launch and no such rows: the kernels write the caller's outputs as before.
 #include "geom.hpp"
 
 namespace {
@@ -35,6 +40,7 @@ struct PostCfg {
   float nms_thresh;
   float range[6];      // post_center_range
   float dir_offset;
+  int num_tasks;       // a kernel's frame index is the virtual frame v = b * num_tasks + t (1: v = b)
 };
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -117,7 +123,9 @@ __global__ __launch_bounds__(SORT_NT) void topk_decode_kernel(const float* __res
     const unsigned aid = (unsigned)(key & 0xFFFFFFFFull);
     const float sc = __uint_as_float(~(unsigned)(key >> 32));
     const int pix = aid / APL, a = aid % APL;
-    const float* an = anchors + ((size_t)(anchors_per_frame ? (size_t)b * anchors_per_frame : 0) + aid) * 7;
+    // anchors (T, A, 7) shared by all frames, or one set per (frame, task)
+    const float* an = anchors + ((size_t)(anchors_per_frame ? (size_t)b * anchors_per_frame
+                                                            : (size_t)(b % C.num_tasks) * (C.num_pix * APL)) + aid) * 7;
     float t[7];
 #pragma unroll
     for (int q = 0; q < 7; ++q) t[q] = hb[(size_t)(a * 7 + q) * C.num_pix + pix];
@@ -310,7 +318,7 @@ __device__ __forceinline__ int finalize_wave(const PostCfg& C, int b, int lane, 
                                              int* __restrict__ out_label, float* rec) {
   double nx[6], ny[6], nz[6], nd[6];
   if (frustum) {
-    const double* f = frustum + (size_t)b * 72;
+    const double* f = frustum + (size_t)(b / C.num_tasks) * 72;  // per real frame
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
       const double* s = f + k * 12;
@@ -502,6 +510,57 @@ __global__ __launch_bounds__(256) void pack_detections_kernel(const float* __res
   if (threadIdx.x == 0 && !base_in) *cursor = c0 + batch;
 }
 
+// Multi-task merge (mg_head_sessd.py:932-937): the detections of frame b are the kept rows of task 0, then task 1, ... each in
+// NMS order, label = task index (one class per task). task_* = the per-(frame, task) rows K5 left in the workspace, stride
+// post_max; outputs (B, T * post_max, ...), rows past out_count[b] are not written. records != nullptr: the frame's record
+// (T * post_max, 9) with zero rows past the count, ring slot (rec_base + b) % capacity (the cursor was advanced by K2).
+__global__ __launch_bounds__(256) void merge_tasks_kernel(int num_tasks, int post_max, const float* __restrict__ task_box,
+                                                           const float* __restrict__ task_score,
+                                                           const int* __restrict__ task_count, float* __restrict__ out_box,
+                                                           float* __restrict__ out_score, int* __restrict__ out_label,
+                                                           int* __restrict__ out_count, int* __restrict__ out_task_count,
+                                                           float* __restrict__ records, int* __restrict__ rec_count, int capacity,
+                                                           const int* __restrict__ rec_base) {
+  const int b = blockIdx.x;
+  int start[5];  // num_tasks <= 4
+  start[0] = 0;
+  for (int t = 0; t < num_tasks; ++t) start[t + 1] = start[t] + min(task_count[b * num_tasks + t], post_max);
+  const int total = start[num_tasks], rows = num_tasks * post_max;
+  float* rec = records ? records + (size_t)((rec_base[0] + b) % capacity) * rows * 9 : nullptr;
+  for (int r = threadIdx.x; r < rows; r += 256) {
+    if (r >= total) {
+      if (rec)
+        for (int q = 0; q < 9; ++q) rec[(size_t)r * 9 + q] = 0.f;
+      continue;
+    }
+    int t = 0;
+    while (r >= start[t + 1]) ++t;
+    const size_t src = (size_t)(b * num_tasks + t) * post_max + (r - start[t]), dst = (size_t)b * rows + r;
+    const float sc = task_score[src];
+    for (int q = 0; q < 7; ++q) {
+      const float v = task_box[src * 7 + q];
+      out_box[dst * 7 + q] = v;
+      if (rec) rec[(size_t)r * 9 + q] = v;
+    }
+    out_score[dst] = sc;
+    out_label[dst] = t;
+    if (rec) {
+      rec[(size_t)r * 9 + 7] = sc;
+      rec[(size_t)r * 9 + 8] = (float)t;
+    }
+  }
+  if (threadIdx.x == 0) {
+    out_count[b] = total;
+    if (rec) rec_count[(rec_base[0] + b) % capacity] = total;
+  }
+  if (out_task_count && threadIdx.x < num_tasks) out_task_count[b * num_tasks + threadIdx.x] = start[threadIdx.x + 1] - start[threadIdx.x];
+}
+
+// single task: out_task_count (B, 1) is out_count (a kernel, not a copy node: see fill.hip)
+__global__ __launch_bounds__(256) void copy_counts_kernel(const int* __restrict__ src, int* __restrict__ dst, int n) {
+  for (int i = threadIdx.x; i < n; i += 256) dst[i] = src[i];
+}
+
 struct PostWs {
   unsigned long long* keys;
   int* count;
@@ -517,9 +576,15 @@ struct PostWs {
   int* rec_base;
   unsigned* pairs;
   int* pair_count;
+  // num_tasks > 1 only: K5's per-(frame, task) rows, merged by merge_tasks_kernel
+  float* task_box;
+  float* task_score;
+  int* task_label;
+  int* task_count;
 };
 
-size_t post_ws_layout(int batch, int num_anchors, int pre_max, int post_max, PostWs* w, char* base) {
+// batch = virtual frames (B * num_tasks); the single-task layout is unchanged
+size_t post_ws_layout(int batch, int num_tasks, int num_anchors, int pre_max, int post_max, PostWs* w, char* base) {
   size_t off = 0;
   auto take = [&](size_t bytes) {
     size_t o = off;
@@ -541,6 +606,13 @@ size_t post_ws_layout(int batch, int num_anchors, int pre_max, int post_max, Pos
   size_t o_rb = take(4);
   size_t o_pairs = take((size_t)batch * rn_pair_cap(pre_max) * 4);
   size_t o_pc = take((size_t)batch * 4);
+  size_t o_tb = 0, o_ts = 0, o_tl = 0, o_tc = 0;
+  if (num_tasks > 1) {
+    o_tb = take((size_t)batch * post_max * 7 * 4);
+    o_ts = take((size_t)batch * post_max * 4);
+    o_tl = take((size_t)batch * post_max * 4);
+    o_tc = take((size_t)batch * 4);
+  }
   if (w) {
     w->keys = (unsigned long long*)(base + o_keys);
     w->count = (int*)(base + o_count);
@@ -556,6 +628,10 @@ size_t post_ws_layout(int batch, int num_anchors, int pre_max, int post_max, Pos
     w->rec_base = (int*)(base + o_rb);
     w->pairs = (unsigned*)(base + o_pairs);
     w->pair_count = (int*)(base + o_pc);
+    w->task_box = (float*)(base + o_tb);
+    w->task_score = (float*)(base + o_ts);
+    w->task_label = (int*)(base + o_tl);
+    w->task_count = (int*)(base + o_tc);
   }
   return off;
 }
@@ -599,33 +675,45 @@ __global__ __launch_bounds__(64) void nms_reduce_batch_kernel(const int* __restr
 
 extern "C" {
 
-size_t sessd_predict_workspace_bytes(int batch, int num_anchors, int pre_max_size, int post_max_size) {
-  return post_ws_layout(batch, num_anchors, pre_max_size, post_max_size, nullptr, nullptr);
+size_t sessd_predict_tasks_workspace_bytes(int batch, int num_tasks, int num_anchors, int pre_max_size, int post_max_size) {
+  if (batch < 1 || num_tasks < 1 || num_tasks > 4) return 0;
+  return post_ws_layout(batch * num_tasks, num_tasks, num_anchors, pre_max_size, post_max_size, nullptr, nullptr);
 }
 
-// head (B,22,H*W) planar, anchors (A,7) shared by all frames (anchors_per_frame = 0) or (B,A,7),
-// frustum (B,1,6,4,3) float64 or NULL. Outputs: out_box (B,post,7), out_score (B,post), out_label (B,post) int32,
-// out_count (B,) -- rows [0,out_count[b]) are the detections of frame b in NMS order.
-// ext_keys / ext_key_count (both or neither): the score-filter keys (B, 2 * num_pixels) uint64 and their per-frame counts were
-// already produced with the head tensor (sessd_ssfa_fuse_head_keys; counts zeroed by the caller before that launch) -- the
-// count clear and the score_filter launch are skipped.
-// records != NULL: every frame also leaves its fixed-size detection record (sessd_pack_detections' layout and ring rule:
-// slot = (*cursor + b) % capacity_frames, *cursor += batch) from inside the last launch.
-// 3 launches per call with external keys and pre_max_size such that the suppression mask fits the LDS (<= ~1280): top-k +
-// decode, suppression mask, greedy walk + filters + record.
-int sessd_predict_fused(const float* head, int batch, int num_pixels, const float* anchors, int anchors_per_frame,
+size_t sessd_predict_workspace_bytes(int batch, int num_anchors, int pre_max_size, int post_max_size) {
+  return post_ws_layout(batch, 1, num_anchors, pre_max_size, post_max_size, nullptr, nullptr);
+}
+
+// head (B,T,22,H*W) planar, T = num_tasks (1..4, one class and two rotations per task); anchors (T,A,7) shared by all frames
+// (anchors_per_frame = 0) or (B,T,A,7) (anchors_per_frame = A), A = 2 * num_pixels per task; frustum (B,1,6,4,3) float64 or
+// NULL, per real frame. Every task applies the score threshold, pre_max_size, the NMS and post_max_size on its own.
+// Outputs: out_box (B,T*post,7), out_score (B,T*post), out_label (B,T*post) int32, out_count (B,) -- rows [0,out_count[b]) are
+// the detections of frame b: task 0's in NMS order, then task 1's, ...; label = task index. out_task_count (B,T) or NULL: the
+// rows each task contributed.
+// ext_keys / ext_key_count (both or neither): the score-filter keys (B*T, 2 * num_pixels) uint64 and their per-(frame, task)
+// counts were already produced with the head tensor (sessd_ssfa_fuse_head_tasks; counts zeroed by the caller before that
+// launch) -- the count clear and the score_filter launch are skipped.
+// records != NULL: every frame also leaves its fixed-size detection record (T*post, 9) (sessd_pack_detections' layout and ring
+// rule: slot = (*cursor + b) % capacity_frames, *cursor += batch) from inside the last launch.
+// T = 1: 3 launches per call with external keys and pre_max_size such that the suppression mask fits the LDS (<= ~1280): top-k
+// + decode, suppression mask, greedy walk + filters + record. T > 1: the same launches over B*T virtual frames + the merge.
+int sessd_predict_tasks(const float* head, int batch, int num_tasks, int num_pixels, const float* anchors, int anchors_per_frame,
                         const double* frustum, float score_thresh, int pre_max_size, int post_max_size, float nms_iou_thresh,
                         const float* post_center_range6, float direction_offset, float* out_box, float* out_score,
-                        int* out_label, int* out_count, const unsigned long long* ext_keys, const int* ext_key_count,
-                        float* records, int* record_counts, int capacity_frames, int* cursor, void* workspace,
-                        size_t workspace_bytes, hipStream_t stream) {
+                        int* out_label, int* out_count, int* out_task_count, const unsigned long long* ext_keys,
+                        const int* ext_key_count, float* records, int* record_counts, int capacity_frames, int* cursor,
+                        void* workspace, size_t workspace_bytes, hipStream_t stream) {
   if (batch < 1 || num_pixels < 1 || pre_max_size < 1 || pre_max_size > 4096 || post_max_size < 1) return SESSD_EINVAL;
+  if (num_tasks < 1 || num_tasks > 4) return SESSD_EINVAL;
   if (pre_max_size > SORT_N - 64) return SESSD_EINVAL;  // running top-k keeps pre_max + a fresh chunk in 2048 slots
   if ((ext_keys == nullptr) != (ext_key_count == nullptr)) return SESSD_EINVAL;
   if (records && (!record_counts || !cursor || capacity_frames < batch || batch > 256)) return SESSD_EINVAL;
   const int A = num_pixels * APL;
+  if (anchors_per_frame && anchors_per_frame != A) return SESSD_EINVAL;
+  const bool multi = num_tasks > 1;
+  const int vbatch = batch * num_tasks;  // virtual frames
   PostWs w;
-  if (post_ws_layout(batch, A, pre_max_size, post_max_size, &w, (char*)workspace) > workspace_bytes)
+  if (post_ws_layout(vbatch, num_tasks, A, pre_max_size, post_max_size, &w, (char*)workspace) > workspace_bytes)
     return SESSD_EWORKSPACE;
   PostCfg C;
   C.num_pix = num_pixels;
@@ -635,26 +723,33 @@ int sessd_predict_fused(const float* head, int batch, int num_pixels, const floa
   C.nms_thresh = nms_iou_thresh;
   for (int i = 0; i < 6; ++i) C.range[i] = post_center_range6[i];
   C.dir_offset = direction_offset;
+  C.num_tasks = num_tasks;
   const unsigned long long* keys = ext_keys;
   const int* key_count = ext_key_count;
   if (!ext_keys) {
-    SESSD_FILL(w.count, 0, batch, stream);
-    SESSD_LAUNCH(score_filter_kernel, dim3(sessd_divup(num_pixels, 256), batch), dim3(256), 0, stream, head, C,
+    SESSD_FILL(w.count, 0, vbatch, stream);
+    SESSD_LAUNCH(score_filter_kernel, dim3(sessd_divup(num_pixels, 256), vbatch), dim3(256), 0, stream, head, C,
                        w.keys, A, w.count);
     SESSD_CHECK_LAUNCH();
     keys = w.keys;
     key_count = w.count;
   }
-  SESSD_LAUNCH(topk_decode_kernel, dim3(batch), dim3(SORT_NT), 0, stream, head, anchors, anchors_per_frame, C,
+  SESSD_LAUNCH(topk_decode_kernel, dim3(vbatch), dim3(SORT_NT), 0, stream, head, anchors, anchors_per_frame, C,
                      keys, A, key_count, w.cand_box, w.cand_score, w.cand_dir, w.corners, w.standup, w.n_top,
                      records ? cursor : (int*)nullptr, w.rec_base, batch, w.pair_count);
   SESSD_CHECK_LAUNCH();
   const int words = sessd_divup(pre_max_size, 64);
   {
-    const int rc = launch_rnms_mask(w.n_top, batch, pre_max_size, nms_iou_thresh, w.corners, w.standup, w.mask, words, w.pairs,
+    const int rc = launch_rnms_mask(w.n_top, vbatch, pre_max_size, nms_iou_thresh, w.corners, w.standup, w.mask, words, w.pairs,
                                     w.pair_count, stream);
     if (rc != SESSD_OK) return rc;
   }
+  // multi-task: K4/K5 leave per-(frame, task) rows in the workspace; the merge writes the caller's outputs and the record
+  float* k_box = multi ? w.task_box : out_box;
+  float* k_score = multi ? w.task_score : out_score;
+  int* k_label = multi ? w.task_label : out_label;
+  int* k_count = multi ? w.task_count : out_count;
+  float* k_records = multi ? nullptr : records;
   const size_t lds = (size_t)pre_max_size * words * 8 + (size_t)post_max_size * 4 + (size_t)post_max_size * 9 * 4;
   if (lds <= 160 * 1024 - 1024) {
     static bool attr_set = false;
@@ -663,24 +758,45 @@ int sessd_predict_fused(const float* head, int batch, int num_pixels, const floa
                                     160 * 1024 - 1024));
       attr_set = true;
     }
-    SESSD_LAUNCH(nms_reduce_finalize_kernel, dim3(batch), dim3(1024), lds, stream, C, w.n_top, w.mask, words, w.cand_box,
-                       w.cand_score, w.cand_dir, frustum, out_box, out_score, out_label, out_count, records, record_counts,
+    SESSD_LAUNCH(nms_reduce_finalize_kernel, dim3(vbatch), dim3(1024), lds, stream, C, w.n_top, w.mask, words, w.cand_box,
+                       w.cand_score, w.cand_dir, frustum, k_box, k_score, k_label, k_count, k_records, record_counts,
                        capacity_frames, w.rec_base);
     SESSD_CHECK_LAUNCH();
-    return SESSD_OK;
+  } else {
+    SESSD_LAUNCH(nms_reduce_batch_kernel, dim3(vbatch), dim3(64), 0, stream, w.n_top, pre_max_size, w.mask, words,
+                       post_max_size, w.keep, w.n_keep);
+    SESSD_CHECK_LAUNCH();
+    SESSD_LAUNCH(finalize_kernel, dim3(vbatch), dim3(64), 0, stream, C, w.keep, w.n_keep, w.cand_box, w.cand_score,
+                       w.cand_dir, frustum, k_box, k_score, k_label, k_count);
+    SESSD_CHECK_LAUNCH();
+    if (k_records) {
+      SESSD_LAUNCH(pack_detections_kernel, dim3(1), dim3(256), 0, stream, out_box, out_score, out_label, out_count, batch,
+                   post_max_size, records, record_counts, capacity_frames, (int*)nullptr, w.rec_base);
+      SESSD_CHECK_LAUNCH();
+    }
   }
-  SESSD_LAUNCH(nms_reduce_batch_kernel, dim3(batch), dim3(64), 0, stream, w.n_top, pre_max_size, w.mask, words,
-                     post_max_size, w.keep, w.n_keep);
-  SESSD_CHECK_LAUNCH();
-  SESSD_LAUNCH(finalize_kernel, dim3(batch), dim3(64), 0, stream, C, w.keep, w.n_keep, w.cand_box, w.cand_score,
-                     w.cand_dir, frustum, out_box, out_score, out_label, out_count);
-  SESSD_CHECK_LAUNCH();
-  if (records) {
-    SESSD_LAUNCH(pack_detections_kernel, dim3(1), dim3(256), 0, stream, out_box, out_score, out_label, out_count, batch,
-                 post_max_size, records, record_counts, capacity_frames, (int*)nullptr, w.rec_base);
+  if (multi) {
+    SESSD_LAUNCH(merge_tasks_kernel, dim3(batch), dim3(256), 0, stream, num_tasks, post_max_size, w.task_box, w.task_score,
+                 w.task_count, out_box, out_score, out_label, out_count, out_task_count, records, record_counts, capacity_frames,
+                 w.rec_base);
+    SESSD_CHECK_LAUNCH();
+  } else if (out_task_count) {  // (B, 1): the frame's count
+    SESSD_LAUNCH(copy_counts_kernel, dim3(1), dim3(256), 0, stream, out_count, out_task_count, batch);
     SESSD_CHECK_LAUNCH();
   }
   return SESSD_OK;
+}
+
+int sessd_predict_fused(const float* head, int batch, int num_pixels, const float* anchors, int anchors_per_frame,
+                        const double* frustum, float score_thresh, int pre_max_size, int post_max_size, float nms_iou_thresh,
+                        const float* post_center_range6, float direction_offset, float* out_box, float* out_score,
+                        int* out_label, int* out_count, const unsigned long long* ext_keys, const int* ext_key_count,
+                        float* records, int* record_counts, int capacity_frames, int* cursor, void* workspace,
+                        size_t workspace_bytes, hipStream_t stream) {
+  return sessd_predict_tasks(head, batch, 1, num_pixels, anchors, anchors_per_frame, frustum, score_thresh, pre_max_size,
+                             post_max_size, nms_iou_thresh, post_center_range6, direction_offset, out_box, out_score, out_label,
+                             out_count, nullptr, ext_keys, ext_key_count, records, record_counts, capacity_frames, cursor,
+                             workspace, workspace_bytes, stream);
 }
 
 int sessd_predict(const float* head, int batch, int num_pixels, const float* anchors, int anchors_per_frame,

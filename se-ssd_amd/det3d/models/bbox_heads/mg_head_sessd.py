@@ -403,18 +403,32 @@ class MultiGroupHead(nn.Module):
     @torch.no_grad()
     def predict(self, example, preds_dicts, test_cfg, **kwargs):
         """Same contract as the reference: list (per sample) of dict(box3d_lidar, scores, label_preds, metadata).
-        Decode, score filter, rotated NMS, frustum / direction / range filters all run on the device in ONE call."""
-        assert len(preds_dicts) == 1 and len(self.num_classes) == 1, "multi-task heads are outside the SE-SSD car config"
-        preds = preds_dicts[0]
-        anchors = example["anchors"][0]
-        B = anchors.shape[0]
-        planar = preds.get("_planar")
-        if planar is None:  # rebuilt from the NHWC tensors of the reference contract
-            parts = [preds["box_preds"], preds["cls_preds"], preds["dir_cls_preds"], preds["iou_preds"]]
-            planar = torch.cat([p.permute(0, 3, 1, 2) for p in parts], 1).contiguous()
+        Decode, score filter, rotated NMS, frustum / direction / range filters all run on the device in ONE call.
+        T tasks (mg_head_sessd.py:893-943): every task with its own anchors example["anchors"][t], the detections concatenated
+        in task order, label = number of classes before the task (one class per task: the task index)."""
+        T = len(preds_dicts)
+        if not 1 <= T <= ops.MAX_TASKS or T != len(self.num_classes):
+            raise ValueError("multi-task inference supports 1 to %d tasks, got %d" % (ops.MAX_TASKS, T))
+        if any(n != 1 for n in self.num_classes):
+            raise ValueError("multi-task inference supports one class per task, got num_classes = %s" % (list(self.num_classes),))
+        B = example["anchors"][0].shape[0]
+        planes = []
+        for preds in preds_dicts:
+            planar = preds.get("_planar")
+            if planar is None:  # rebuilt from the NHWC tensors of the reference contract
+                parts = [preds["box_preds"], preds["cls_preds"], preds["dir_cls_preds"], preds["iou_preds"]]
+                planar = torch.cat([p.permute(0, 3, 1, 2) for p in parts], 1)
+            if planar.shape[1] != ops.TASK_HEAD_CH:
+                raise ValueError("multi-task inference supports two rotations per location (22 head channels per task), got %d"
+                                 % planar.shape[1])
+            planes.append(planar)
+        planar = (planes[0] if T == 1 else torch.cat(planes, 1)).contiguous()
         Bc, C, H, W = planar.shape
         head = planar.reshape(Bc, C, H * W).float().contiguous()
-        anc = anchors.reshape(B, -1, self.box_n_dim).float().contiguous()
+        if T == 1:
+            anc = example["anchors"][0].reshape(B, -1, self.box_n_dim).float().contiguous()
+        else:  # (B, T, A, 7)
+            anc = torch.stack([example["anchors"][t].reshape(B, -1, self.box_n_dim).float() for t in range(T)], 1).contiguous()
         frustum = None
         calib = example.get("calib")
         if calib is not None and "frustum" in calib:
@@ -422,7 +436,7 @@ class MultiGroupHead(nn.Module):
         nms = test_cfg["nms"] if isinstance(test_cfg, dict) else test_cfg.nms
         out = ops.predict(head, anc, frustum, float(self.thresh), int(nms["nms_pre_max_size"]),
                           int(nms["nms_post_max_size"]), float(nms["nms_iou_threshold"]), self.post_center_range,
-                          float(self.direction_offset))
+                          float(self.direction_offset), num_tasks=T)
         counts = out["count"].cpu().tolist()  # the single host read of the whole predict path
         meta = example.get("metadata", [None] * B)
         ret = []

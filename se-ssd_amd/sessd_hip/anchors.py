@@ -25,6 +25,18 @@ def create_anchors_3d_range(feature_size=(1, 200, 176), anchor_range=(0, -40.0, 
     return out
 
 
+def create_task_anchors(feature_hw, tasks, anchor_range_xy=(0, -40.0, 70.4, 40.0), dtype=np.float32):
+    """(T, H*W*num_rot, 7): one anchor set per task of a multi-task head, in task order. tasks: list of dict(sizes=(w, l, h),
+    z=<anchor centre height>, rotations=(0, 1.57)) -- the per-class anchor generators of a multi-class KITTI config."""
+    H, W = [int(v) for v in feature_hw]
+    x0, y0, x1, y1 = anchor_range_xy
+    out = []
+    for t in tasks:
+        rng = (x0, y0, t["z"], x1, y1, t["z"])
+        out.append(create_anchors_3d_range((1, H, W), rng, t["sizes"], t.get("rotations", (0, 1.57)), dtype).reshape(-1, 7))
+    return np.stack(out)
+
+
 def projection_matrix_to_CRT_kitti(proj):
     CR, CT = proj[0:3, 0:3], proj[0:3, 3]
     Rinv, Cinv = np.linalg.qr(np.linalg.inv(CR))

@@ -6,8 +6,29 @@ import logging
 from det3d.builder import build_box_coder
 
 
-def kitti_car_model():
-    tasks = [dict(num_class=1, class_names=["Car"])]
+# Three-class KITTI variant (one task per class, as MultiGroupHead builds one Head per task): per-task anchor box sizes
+# (w, l, h) and anchor centre heights; two rotations per location each.
+KITTI_3CLASS_TASKS = [dict(num_class=1, class_names=["Car"]), dict(num_class=1, class_names=["Pedestrian"]),
+                      dict(num_class=1, class_names=["Cyclist"])]
+KITTI_3CLASS_ANCHORS = [dict(sizes=(1.6, 3.9, 1.56), z=-1.0, rotations=(0, 1.57)),
+                        dict(sizes=(0.6, 0.8, 1.73), z=-0.6, rotations=(0, 1.57)),
+                        dict(sizes=(0.6, 1.76, 1.73), z=-0.6, rotations=(0, 1.57))]
+
+
+def kitti_3class_model():
+    """kitti_car_model() with tasks = [Car, Pedestrian, Cyclist]: inference only (the losses are single-task)."""
+    return kitti_car_model(tasks=KITTI_3CLASS_TASKS)
+
+
+def kitti_3class_anchors(feature_hw=(200, 176), voxel_range=None):
+    """(3, H*W*2, 7) anchors of KITTI_3CLASS_ANCHORS over the x / y extent of `voxel_range` (default: the KITTI range)."""
+    from .anchors import create_task_anchors
+    r = VOXEL_GENERATOR["range"] if voxel_range is None else voxel_range
+    return create_task_anchors(feature_hw, KITTI_3CLASS_ANCHORS, (r[0], r[1], r[3], r[4]))
+
+
+def kitti_car_model(tasks=None):
+    tasks = [dict(num_class=1, class_names=["Car"])] if tasks is None else [dict(t) for t in tasks]
     box_coder = dict(type="ground_box3d_coder", n_dim=7, linear_dim=False, encode_angle_vector=False)
     return dict(
         type="VoxelNet", pretrained=None,
@@ -15,7 +36,7 @@ def kitti_car_model():
         backbone=dict(type="SpMiddleFHD", num_input_features=4, ds_factor=8, norm_cfg=None),
         neck=dict(type="SSFA", layer_nums=[5], ds_layer_strides=[1], ds_num_filters=[128], us_layer_strides=[1],
                   us_num_filters=[128], num_input_features=128, norm_cfg=None, logger=logging.getLogger("RPN")),
-        bbox_head=dict(type="MultiGroupHead", mode="3d", in_channels=128, norm_cfg=None, tasks=tasks, weights=[1],
+        bbox_head=dict(type="MultiGroupHead", mode="3d", in_channels=128, norm_cfg=None, tasks=tasks, weights=[1] * len(tasks),
                        box_coder=build_box_coder(box_coder), encode_background_as_zeros=True,
                        loss_norm=dict(type="NormByNumPositives", pos_cls_weight=1.0, neg_cls_weight=1.0),
                        loss_cls=dict(type="SigmoidFocalLoss", alpha=0.25, gamma=2.0, loss_weight=1.0),
@@ -34,18 +55,23 @@ VOXEL_GENERATOR = dict(range=[0, -40.0, -3.0, 70.4, 40.0, 1.0], voxel_size=[0.05
                        max_voxel_num=20000)
 
 
-def build_synthetic_detector(device, seed=0, calib_frame_seed=0, max_voxels=16000, num_points=20000, supersample=1):
+def build_synthetic_detector(device, seed=0, calib_frame_seed=0, max_voxels=16000, num_points=20000, supersample=1,
+                             model_cfg=None, voxel_range=None):
     """det3d-mirror VoxelNet with seeded weights, BatchNorm statistics calibrated on one synthetic frame (on `device`) of the
     workload's own density (supersample = 3 for the 200 k-point dense scenes): random weights calibrated on a sparse scan give
-    activations (and decoded boxes) of absurd magnitude on a dense one."""
+    activations (and decoded boxes) of absurd magnitude on a dense one.
+    model_cfg: another model dict (kitti_3class_model()); voxel_range: a reduced range (the frame is cropped by the voxelizer)."""
     import torch
     from det3d.models import build_detector
     from . import ops, synth
-    model = build_detector(kitti_car_model(), train_cfg=None, test_cfg=TEST_CFG)
+    model = build_detector(kitti_car_model() if model_cfg is None else model_cfg, train_cfg=None, test_cfg=TEST_CFG)
     synth.init_synthetic_weights(model, seed)
     model.to(device)
     pts = torch.from_numpy(synth.make_frame(calib_frame_seed, num_points, supersample=supersample)).to(device)
-    r = ops.voxelize_batch([pts], VOXEL_GENERATOR["voxel_size"], VOXEL_GENERATOR["range"], 5, max_voxels)
+    vr = VOXEL_GENERATOR["range"] if voxel_range is None else voxel_range
+    vs = VOXEL_GENERATOR["voxel_size"]
+    r = ops.voxelize_batch([pts], vs, vr, 5, max_voxels)
     m = int(r["prefix"][1].item())
-    synth.calibrate_synthetic_model(model, r["mean"][:m].contiguous(), r["coors"][:m].contiguous(), 1, [1408, 1600, 40])
+    grid = [int(round((vr[i + 3] - vr[i]) / vs[i])) for i in range(3)]  # [1408, 1600, 40] for the KITTI range
+    synth.calibrate_synthetic_model(model, r["mean"][:m].contiguous(), r["coors"][:m].contiguous(), 1, grid)
     return model

@@ -113,10 +113,29 @@ def active_tile_constants(neck):
     return chain
 
 
+def pack_task_heads(head_tasks):
+    """The 1x1 heads of T tasks as ONE conv: per task [conv_box 14 | conv_cls 2 | conv_dir 4 | conv_iou 2] = 22 channels, the
+    tasks one after the other -> weight (T * 22, C, 1, 1), bias (T * 22). The limits of the multi-task inference path are
+    checked here: 1 to 4 tasks, one class per task, two rotations per location."""
+    import torch.nn as nn
+    if isinstance(head_tasks, nn.Module) and not isinstance(head_tasks, nn.ModuleList):
+        head_tasks = [head_tasks]
+    ops.check_num_tasks(len(head_tasks))
+    ws, bs = [], []
+    for t, h in enumerate(head_tasks):
+        convs = [h.conv_box, h.conv_cls, h.conv_dir, h.conv_iou]
+        if [c.out_channels for c in convs] != [14, 2, 4, 2]:
+            raise ValueError("multi-task inference supports one class per task and two rotations per location (head channels "
+                             "14 box + 2 cls + 4 dir + 2 iou); task %d has %s" % (t, [c.out_channels for c in convs]))
+        ws += [c.weight for c in convs]
+        bs += [c.bias for c in convs]
+    return torch.cat(ws, 0), torch.cat(bs, 0)
+
+
 class DensePlan:
     """SSFA neck + head lowered to conv launches (det3d/models/necks/rpn_v1.py:135-235, mg_head_sessd.py:202-230)."""
 
-    def __init__(self, neck, head_task, device):
+    def __init__(self, neck, head_tasks, device):
         def cbr(seq, ci, bi, deconv=False):
             conv, bn = seq[ci], seq[bi]
             w = conv.weight.detach().to(device)
@@ -144,14 +163,13 @@ class DensePlan:
         s0, t0 = fold_bn(neck.w_0[1])
         s1, t1 = fold_bn(neck.w_1[1])
         self.wbn = (float(s0), float(t0), float(s1), float(t1))  # host scalars, read once at plan time
-        # four 1x1 heads fused into one 22-channel conv: [box 14 | cls 2 | dir 4 | iou 2]
-        hw = torch.cat([head_task.conv_box.weight, head_task.conv_cls.weight, head_task.conv_dir.weight,
-                        head_task.conv_iou.weight], 0).detach().to(device)
-        hb = torch.cat([head_task.conv_box.bias, head_task.conv_cls.bias, head_task.conv_dir.bias,
-                        head_task.conv_iou.bias], 0).detach().to(device).float().contiguous()
-        assert hw.shape[0] == 22, "engine supports the single-task car head (14+2+4+2 channels)"
+        # per task the four 1x1 heads fused into one 22-channel conv [box 14 | cls 2 | dir 4 | iou 2]; the tasks one after the
+        # other (task-major channels): (T * 22, C)
+        hw, hb = pack_task_heads(head_tasks)
+        hw, hb = hw.detach().to(device), hb.detach().to(device).float().contiguous()
+        self.num_tasks = hw.shape[0] // ops.TASK_HEAD_CH
         self.head = (ops.pack_conv2d(hw), None, hb)
-        self.head_w = hw.reshape(22, -1).float().contiguous()  # row-major (22, C): the fused SSFA-tail + heads launch
+        self.head_w = hw.reshape(hw.shape[0], -1).float().contiguous()  # row-major (T * 22, C): the fused SSFA-tail + heads launch
         self.head_b = hb
 
 
@@ -178,7 +196,8 @@ class InferenceEngine:
         convs = [m for m in model.backbone.middle_conv if hasattr(m, "indice_key")]
         bns = [m for m in model.backbone.middle_conv if isinstance(m, torch.nn.BatchNorm1d)]
         self.sp = SparsePlan(convs, bns, SPMIDDLE_LAYERS, dev)
-        self.dn = DensePlan(model.neck, model.bbox_head.tasks[0], dev)
+        self.dn = DensePlan(model.neck, model.bbox_head.tasks, dev)
+        T = self.num_tasks = self.dn.num_tasks  # (frame, task) goes through predict as the virtual frame b * T + t
         nms = test_cfg["nms"] if isinstance(test_cfg, dict) else test_cfg.nms
         self.score_thresh = float(test_cfg["score_threshold"])
         self.pre_max = int(nms["nms_pre_max_size"])
@@ -233,8 +252,8 @@ class InferenceEngine:
                 li += 1
         chain_bytes = ops.SparseChain.workspace_bytes(self.sparse_shape, steps, [L["cap"] for L in self.levels[1:]], B)
         # control words + the chain's occupancy maps, cleared to 0 by the frame's one clear launch: prefix[B+1] | (unused) |
-        # key_count[B] (candidates of the score filter that runs inside the head launch) | maps
-        n_ctrl = (2 * B + 2 + 63) // 64 * 64
+        # key_count[B * T] (candidates per (frame, task) of the score filter that runs inside the head launch) | maps
+        n_ctrl = (B + 2 + B * T + 63) // 64 * 64
         self.zero_arena = torch.zeros((n_ctrl + (chain_bytes + 3) // 4,), dtype=i32, device=dev)
         self.ctrl = self.zero_arena[:n_ctrl]
         self.prefix = self.ctrl[:B + 1]
@@ -243,7 +262,7 @@ class InferenceEngine:
         # (round-3 advisor finding: inside the arena the next frame's clear erased it). results() / the pipeline clear it when
         # they raise.
         self.err = torch.zeros((1,), dtype=i32, device=dev)
-        self.key_count = self.ctrl[B + 2:2 * B + 2]
+        self.key_count = self.ctrl[B + 2:B + 2 + B * T]
         self.chain = ops.SparseChain(self.sparse_shape, steps, [L["cap"] for L in self.levels[1:]], B, jobs, dev,
                                      workspace_tensor=self.zero_arena[n_ctrl:].view(torch.uint8))
         # offset-pattern tiles (sort_tiles=True): the chain also sorts the sites of every 256-row group by neighbour pattern (one
@@ -289,17 +308,30 @@ class InferenceEngine:
             self.t[k] = self.t[src][:B] if k.endswith("0") else self.t[src][B:]
         self.merge_branch_convs = True  # conv_0 + conv_1 as one stream-K Winograd launch when both were tuned to the same shape
         self.h = {k: E(B, 256, H // 2, W // 2) for k in ("a", "b", "x1", "tr1")}
-        self.head = E(B, 22, H * W)
+        self.head = E(B, T * 22, H * W)
         if anchors is None:
+            if T > 1:
+                raise ValueError("a %d-task head needs its anchors: pass anchors=(T, H*W*2, 7), one set per task in task order "
+                                 "(sessd_hip.anchors.create_task_anchors), here H, W = %d, %d" % (T, H, W))
             from .anchors import create_anchors_3d_range
             anchors = create_anchors_3d_range((1, H, W)).reshape(-1, 7)
+        if T > 1:
+            if isinstance(anchors, (list, tuple)):
+                anchors = torch.stack([torch.as_tensor(a, dtype=f32).reshape(-1, 7) for a in anchors])
+            anchors = torch.as_tensor(anchors, dtype=f32)
+            if tuple(anchors.shape) != (T, 2 * H * W, 7):
+                raise ValueError("anchors of a %d-task head: (%d, %d, 7), one set per task in task order, got %s"
+                                 % (T, T, 2 * H * W, tuple(anchors.shape)))
         self.anchors = torch.as_tensor(anchors, dtype=f32).to(dev).contiguous()
         self.frustum = torch.zeros((B, 1, 6, 4, 3), dtype=torch.float64, device=dev) if use_frustum else None
-        self.out = dict(box=E(B, self.post_max, 7), score=E(B, self.post_max), label=E(B, self.post_max, dt=i32),
+        # T tasks: each keeps up to post_max rows; a frame's rows are task 0's, then task 1's, ... (label = task)
+        self.out = dict(box=E(B, T * self.post_max, 7), score=E(B, T * self.post_max), label=E(B, T * self.post_max, dt=i32),
                         count=torch.zeros((B,), dtype=i32, device=dev))
-        self.pred_ws = torch.empty(int(lib.sessd_predict_workspace_bytes(B, 2 * H * W, self.pre_max, self.post_max)),
+        if T > 1:
+            self.out["task_count"] = torch.zeros((B, T), dtype=i32, device=dev)
+        self.pred_ws = torch.empty(int(lib.sessd_predict_tasks_workspace_bytes(B, T, 2 * H * W, self.pre_max, self.post_max)),
                                    dtype=torch.uint8, device=dev)
-        self.keys = torch.empty((B, 2 * H * W), dtype=torch.int64, device=dev)  # score-filter keys written by the head launch
+        self.keys = torch.empty((B * T, 2 * H * W), dtype=torch.int64, device=dev)  # score-filter keys written by the head launch
         self.fuse_predict = True  # score filter inside the head launch; NMS walk + filters + record in one launch
         self.batched_voxelizer = True  # the frames of a batch in four launches (False: four per frame, as round 3)
         # The neighbour table of the voxels (level 0, hash lookups) and the two submanifold convs that use it depend on the
@@ -1029,17 +1061,30 @@ class InferenceEngine:
             fused_keys = True
             ops.ssfa_fuse_head(o0, o1, d.w0, d.w1, *d.wbn, d.head_w, d.head_b, head_out=self.head,
                                out=t["out"] if self.keep_ssfa else None, score_thresh=self.score_thresh,
-                               keys=self.keys if self.fuse_predict else None, key_count=self.key_count if self.fuse_predict else None)
+                               keys=self.keys if self.fuse_predict else None, key_count=self.key_count if self.fuse_predict else None,
+                               num_tasks=self.num_tasks)
             if self._kmarks is not None:
                 e1.record()
                 self._kmarks.append(("ssfa_tail+head", e0, e1))
         else:
             ops.ssfa_fuse(o0, o1, d.w0, d.w1, *d.wbn, out=t["out"])
-            self._conv(t["out"], d.head, self.head.view(B, 22, self.H, self.W), relu=False, name="head")
+            self._conv(t["out"], d.head, self.head.view(B, self.num_tasks * 22, self.H, self.W), relu=False, name="head")
         self._mark("ssfa_head")
         # ---- predict (a11-a14): top-k + decode, suppression mask, greedy walk + filters (+ the frame's record): 3 launches
         use_keys = fused_keys and self.fuse_predict
         rec = self.records is not None
+        if self.num_tasks > 1:  # the same launches over B * T virtual frames + the merge in task order
+            check(lib.sessd_predict_tasks(self.head.data_ptr(), B, self.num_tasks, self.H * self.W, self.anchors.data_ptr(), 0,
+                                          0 if self.frustum is None else self.frustum.data_ptr(), self.score_thresh, self.pre_max,
+                                          self.post_max, self.nms_thresh, self.post_range.data_ptr(), self.dir_offset,
+                                          self.out["box"].data_ptr(), self.out["score"].data_ptr(), self.out["label"].data_ptr(),
+                                          self.out["count"].data_ptr(), self.out["task_count"].data_ptr(),
+                                          self.keys.data_ptr() if use_keys else 0, self.key_count.data_ptr() if use_keys else 0,
+                                          self.records.data_ptr() if rec else 0, self.record_counts.data_ptr() if rec else 0,
+                                          self.records.shape[0] if rec else 0, self.record_cursor.data_ptr() if rec else 0,
+                                          self.pred_ws.data_ptr(), self.pred_ws.numel(), s), "predict_tasks")
+            self._mark("predict")
+            return self.out
         check(lib.sessd_predict_fused(self.head.data_ptr(), B, self.H * self.W, self.anchors.data_ptr(), 0,
                                       0 if self.frustum is None else self.frustum.data_ptr(), self.score_thresh, self.pre_max,
                                       self.post_max, self.nms_thresh, self.post_range.data_ptr(), self.dir_offset,
@@ -1053,10 +1098,10 @@ class InferenceEngine:
         return self.out
 
     def attach_records(self, capacity_frames):
-        """Keep every frame's detections on the device as a fixed-size record (capacity_frames, post_max, 9) [box 7 | score |
-        label] + counts, appended by the frame itself (also inside a captured graph; call before capture())."""
+        """Keep every frame's detections on the device as a fixed-size record (capacity_frames, num_tasks * post_max, 9) [box 7 |
+        score | label] + counts, appended by the frame itself (also inside a captured graph; call before capture())."""
         cap = max(int(capacity_frames), self.B)
-        self.records = torch.zeros((cap, self.post_max, 9), dtype=torch.float32, device=self.dev)
+        self.records = torch.zeros((cap, self.num_tasks * self.post_max, 9), dtype=torch.float32, device=self.dev)
         self.record_counts = torch.zeros((cap,), dtype=torch.int32, device=self.dev)
         self.record_cursor = torch.zeros((1,), dtype=torch.int32, device=self.dev)
         return self.records, self.record_counts

@@ -2162,26 +2162,51 @@ def split_nhwc(y, sizes):
     return SplitNhwcFunction.apply(y, *[int(v) for v in sizes])
 
 
+MAX_TASKS = 4        # multi-task inference: tasks per head (sessd_ssfa_fuse_head_tasks / sessd_predict_tasks)
+TASK_HEAD_CH = 22    # planar head channels of one task: [box 14 | cls 2 | dir 4 | iou 2], one class, two rotations per location
+
+
+def check_num_tasks(num_tasks):
+    """The limit of the multi-task inference path, as a ValueError that names it."""
+    if not 1 <= int(num_tasks) <= MAX_TASKS:
+        raise ValueError("multi-task inference supports 1 to %d tasks, got %d" % (MAX_TASKS, int(num_tasks)))
+    return int(num_tasks)
+
+
 def ssfa_fuse_head(x0, x1, w0, w1, s0, t0, s1, t1, head_w, head_b, head_out=None, out=None, score_thresh=0.0, keys=None,
-                   key_count=None):
+                   key_count=None, num_tasks=1):
     """ssfa_fuse + the 1x1 heads in one launch: head_w (22, C) row-major, head_b (22) or None -> head_out (B, 22, H*W) planar.
     `out` (B, C, H, W): optional buffer that receives the SSFA output (not written when None).
     keys (B, 2*H*W) int64 + key_count (B,) int32 (zeroed by the caller): the launch also appends predict's score-filter keys
-    (sessd_ssfa_fuse_head_keys) -- the inputs predict_fused() takes instead of running its own score filter."""
+    (sessd_ssfa_fuse_head_keys) -- the inputs predict_fused() takes instead of running its own score filter.
+    num_tasks = T > 1 (sessd_ssfa_fuse_head_tasks): head_w (T*22, C), head_b (T*22) or None -> head_out (B, T*22, H*W) =
+    (B, T, 22, H*W), task t's planes bit-equal to the single-task call with task t's weights; keys (B, T, 2*H*W) and key_count
+    (B*T,) per (frame, task)."""
     _req(x0, torch.float32, "x0")
     _req(x1, torch.float32, "x1")
     _req(head_w, torch.float32, "head_w")
     B, C, H, W = x0.shape
     nout = head_w.shape[0]
+    T = check_num_tasks(num_tasks)
+    if T > 1 and (nout != T * TASK_HEAD_CH or (head_b is not None and head_b.numel() != nout)):
+        raise ValueError("multi-task head weights must be (num_tasks * 22, C) with a (num_tasks * 22) bias: %d channels for %d tasks"
+                         % (nout, T))
     if head_out is None:
         head_out = torch.empty((B, nout, H * W), dtype=torch.float32, device=x0.device)
     if keys is not None:
         assert key_count is not None and keys.dtype == torch.int64 and key_count.dtype == torch.int32 and keys.is_contiguous()
-        assert keys.numel() >= B * 2 * H * W and key_count.numel() >= B
-    check(lib.sessd_ssfa_fuse_head_keys(x0.data_ptr(), x1.data_ptr(), w0.data_ptr(), w1.data_ptr(), float(s0), float(t0), float(s1),
-                                        float(t1), B, C, H * W, _p(out), head_w.data_ptr(), _p(head_b), nout, head_out.data_ptr(),
-                                        float(score_thresh), _p(keys), 2 * H * W if keys is not None else 0, _p(key_count),
-                                        _stream()), "ssfa_fuse_head_keys")
+        assert keys.numel() >= B * T * 2 * H * W and key_count.numel() >= B * T
+    if T == 1:
+        check(lib.sessd_ssfa_fuse_head_keys(x0.data_ptr(), x1.data_ptr(), w0.data_ptr(), w1.data_ptr(), float(s0), float(t0), float(s1),
+                                            float(t1), B, C, H * W, _p(out), head_w.data_ptr(), _p(head_b), nout, head_out.data_ptr(),
+                                            float(score_thresh), _p(keys), 2 * H * W if keys is not None else 0, _p(key_count),
+                                            _stream()), "ssfa_fuse_head_keys")
+        return head_out
+    assert head_out.numel() >= B * nout * H * W and head_out.is_contiguous() and head_w.is_contiguous()
+    check(lib.sessd_ssfa_fuse_head_tasks(x0.data_ptr(), x1.data_ptr(), w0.data_ptr(), w1.data_ptr(), float(s0), float(t0), float(s1),
+                                         float(t1), B, C, H * W, _p(out), head_w.data_ptr(), _p(head_b), T, head_out.data_ptr(),
+                                         float(score_thresh), _p(keys), 2 * H * W if keys is not None else 0, _p(key_count),
+                                         _stream()), "ssfa_fuse_head_tasks")
     return head_out
 
 
@@ -2199,15 +2224,22 @@ def fill_multi(segments):
 # ------------------------------------------------------------------ predict / post-processing
 def predict(head, anchors, frustum=None, score_thresh=0.3, pre_max=1000, post_max=100, nms_thresh=0.01,
             post_center_range=(0, -40.0, -5.0, 70.4, 40.0, 5.0), direction_offset=0.0, out=None, keys=None, key_count=None,
-            records=None):
+            records=None, num_tasks=1):
     """head (B,22,P) planar float32; anchors (A,7) or (B,A,7); frustum (B,1,6,4,3) float64 or None.
     Returns dict(box (B,post,7), score (B,post), label (B,post) int32, count (B,) int32), all on the device.
     keys / key_count: the score-filter keys already produced by ssfa_fuse_head(keys=...) (sessd_predict_fused skips its own
     filter); records = (records (F,post,9) float32, counts (F,) int32, cursor (1,) int32): the call's last launch also appends the
-    frames' detection records to that ring."""
+    frames' detection records to that ring.
+    num_tasks = T > 1 (sessd_predict_tasks): head (B,T*22,P) = (B,T,22,P); anchors (T,A,7) shared by the frames or (B,T,A,7);
+    every task runs its own score filter, top-k, NMS and post_max. Returns box (B,T*post,7), score / label (B,T*post), count (B,)
+    -- task 0's detections in NMS order, then task 1's, ...; label = task index -- and task_count (B,T); records (F,T*post,9)."""
     _req(head, torch.float32, "head")
     _req(anchors, torch.float32, "anchors")
     B, ch, P = head.shape
+    T = check_num_tasks(num_tasks)
+    if T > 1:
+        return _predict_tasks(head, anchors, frustum, score_thresh, pre_max, post_max, nms_thresh, post_center_range,
+                              direction_offset, out, keys, key_count, records, T)
     assert ch == 22
     per_frame = 0
     if anchors.dim() == 3:
@@ -2233,6 +2265,44 @@ def predict(head, anchors, frustum=None, score_thresh=0.3, pre_max=1000, post_ma
                                   out["count"].data_ptr(), _p(keys), _p(key_count), _p(rec), _p(rcnt),
                                   int(rec.shape[0]) if rec is not None else 0, _p(rcur), ws.data_ptr(), ws.numel(), _stream()),
           "predict_fused")
+    return out
+
+
+def _predict_tasks(head, anchors, frustum, score_thresh, pre_max, post_max, nms_thresh, post_center_range, direction_offset, out,
+                   keys, key_count, records, T):
+    B, ch, P = head.shape
+    if ch != T * TASK_HEAD_CH:
+        raise ValueError("multi-task predict takes 22 planar head channels per task (one class, two rotations per location): "
+                         "%d channels for %d tasks" % (ch, T))
+    per_frame = 0
+    if anchors.dim() == 4:
+        per_frame = anchors.shape[2]
+        assert anchors.shape[0] == B
+    assert anchors.dim() in (3, 4) and tuple(anchors.shape[-3:]) == (T, 2 * P, 7), "anchors: (T, 2*P, 7) or (B, T, 2*P, 7)"
+    if frustum is not None:
+        _req(frustum, torch.float64, "frustum")
+        assert frustum.numel() == B * 72
+    dev = head.device
+    if out is None:
+        out = dict(box=torch.empty((B, T * post_max, 7), dtype=torch.float32, device=dev),
+                   score=torch.empty((B, T * post_max), dtype=torch.float32, device=dev),
+                   label=torch.empty((B, T * post_max), dtype=torch.int32, device=dev),
+                   count=torch.empty((B,), dtype=torch.int32, device=dev),
+                   task_count=torch.empty((B, T), dtype=torch.int32, device=dev))
+    assert out["box"].numel() >= B * T * post_max * 7 and out["score"].numel() >= B * T * post_max
+    if keys is not None:
+        assert key_count is not None and keys.numel() >= B * T * 2 * P and key_count.numel() >= B * T
+    ws = workspace(lib.sessd_predict_tasks_workspace_bytes(B, T, 2 * P, pre_max, post_max), dev, "predict")
+    rng = torch.tensor(post_center_range, dtype=torch.float32)
+    rec, rcnt, rcur = records if records is not None else (None, None, None)
+    if rec is not None:
+        assert rec.shape[1] == T * post_max and rec.shape[2] == 9, "records: (frames, num_tasks * post_max, 9)"
+    check(lib.sessd_predict_tasks(head.data_ptr(), B, T, P, anchors.data_ptr(), per_frame, _p(frustum), float(score_thresh),
+                                  pre_max, post_max, float(nms_thresh), rng.data_ptr(), float(direction_offset),
+                                  out["box"].data_ptr(), out["score"].data_ptr(), out["label"].data_ptr(),
+                                  out["count"].data_ptr(), _p(out.get("task_count")), _p(keys), _p(key_count), _p(rec), _p(rcnt),
+                                  int(rec.shape[0]) if rec is not None else 0, _p(rcur), ws.data_ptr(), ws.numel(), _stream()),
+          "predict_tasks")
     return out
 
 

@@ -89,7 +89,7 @@ class HostFedPipeline:
         self.ring, self.fetch_every, self.eager = int(ring), int(fetch_every), bool(eager)
         assert copy_mode in ("instream", "copystream")
         self.copy_mode = copy_mode
-        self.post_max = self.engines[0].post_max
+        self.post_max = self.engines[0].post_max * self.engines[0].num_tasks   # rows of a frame's record (every task keeps post_max)
         cap = 2 * self.fetch_every
         self._st = []
         for e in self.engines:

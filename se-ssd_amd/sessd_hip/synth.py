@@ -183,13 +183,13 @@ def init_synthetic_weights(model, seed=0):
                 m.bias.copy_(torch.rand(c, generator=g) * 0.2 - 0.1)
                 m.running_mean.zero_()
                 m.running_var.fill_(1.0)
-        head = model.bbox_head.tasks[0]
-        head.conv_box.weight.mul_(0.3)
-        head.conv_box.bias.zero_()
-        head.conv_dir.bias.zero_()
-        head.conv_iou.bias.fill_(0.5)
-        head.conv_iou.weight.mul_(0.3)
-        head.conv_cls.bias.zero_()
+        for head in model.bbox_head.tasks:
+            head.conv_box.weight.mul_(0.3)
+            head.conv_box.bias.zero_()
+            head.conv_dir.bias.zero_()
+            head.conv_iou.bias.fill_(0.5)
+            head.conv_iou.weight.mul_(0.3)
+            head.conv_cls.bias.zero_()
     model.eval()
     return model
 
@@ -226,16 +226,16 @@ def calibrate_synthetic_model(model, voxel_features, coors, batch_size, input_sh
             o0, o1 = nk.conv_0(m0), nk.conv_1(m1)
             w = torch.softmax(torch.cat([nk.w_0(o0), nk.w_1(o1)], 1), 1)
             out = o0 * w[:, 0:1] + o1 * w[:, 1:]
-            head = model.bbox_head.tasks[0]
-            head.conv_cls.bias.zero_()
-            logits = F.conv2d(out, head.conv_cls.weight).reshape(-1)
-            q = torch.quantile(logits.float().cpu(), 1.0 - pass_fraction)
-            head.conv_cls.bias.fill_(float(math.log(0.3 / 0.7) - q))
-            # box codes ~N(0, 0.1) and IoU predictions ~N(0.5, 0.15): plausible, well-conditioned boxes
-            for conv, target, bias in ((head.conv_box, 0.1, 0.0), (head.conv_iou, 0.15, 0.5), (head.conv_dir, 1.0, 0.0)):
-                y = F.conv2d(out, conv.weight)
-                conv.weight.mul_(target / float(y.std().clamp_min(1e-6)))
-                conv.bias.fill_(bias)
+            for head in model.bbox_head.tasks:  # every task of a multi-task head gets its own candidates
+                head.conv_cls.bias.zero_()
+                logits = F.conv2d(out, head.conv_cls.weight).reshape(-1)
+                q = torch.quantile(logits.float().cpu(), 1.0 - pass_fraction)
+                head.conv_cls.bias.fill_(float(math.log(0.3 / 0.7) - q))
+                # box codes ~N(0, 0.1) and IoU predictions ~N(0.5, 0.15): plausible, well-conditioned boxes
+                for conv, target, bias in ((head.conv_box, 0.1, 0.0), (head.conv_iou, 0.15, 0.5), (head.conv_dir, 1.0, 0.0)):
+                    y = F.conv2d(out, conv.weight)
+                    conv.weight.mul_(target / float(y.std().clamp_min(1e-6)))
+                    conv.bias.fill_(bias)
     finally:
         for h in hooks:
             h.remove()

@@ -709,6 +709,31 @@ int sessd_predict_tasks(const float* head, int batch, int num_tasks, int num_pix
                         const unsigned long long* ext_keys, const int32_t* ext_key_count, float* records,
                         int32_t* record_counts, int capacity_frames, int32_t* cursor, void* workspace, size_t workspace_bytes,
                         sessd_stream_t stream);
+/* sessd_predict_tasks with DI-NMS as the post-processor of every (frame, task): the other branch of get_task_detections
+ * (mg_head_sessd.py:999-1018, box_torch_ops.rotate_weighted_nms with enable_centerness=True, centerness_c=False). Candidates as
+ * in sessd_predict_tasks (score filter, IoU rectification, top pre_max_size); then per virtual frame, all on the device with the
+ * candidate count never leaving it: score_j *= (1 - softmax_j(|xy_j - anchor xy_j|))^centerness_pow (float32, max subtracted),
+ * the core of nms_cpu.h:173-384 exactly as sessd_di_nms runs it with centerness_c = 0 (picks by the damped score, cnt summed in
+ * box order, weighted-average boxes, suppress on overlap >= suppressed_thresh, keep when cnt > cnt_thresh), then frustum,
+ * direction fix (the picked box's direction label) and centre-range mask on the AVERAGED boxes; score = the largest normalised
+ * score of the pass * the normalisation maximum. Same arguments, outputs, record ring and multi-task merge as
+ * sessd_predict_tasks; nms_iou_thresh is accepted and never read, like the reference's iou_threshold. pre_max_size <= 1024.
+ * Two deviations from the reference: (1) the anchors are the task's own (the reference reads task 0's x, y for every task --
+ * the same grid in the KITTI configs); (2) CAPACITY: the reference wrapper ignores post_max_size, the outputs here hold
+ * post_max_size rows per task, so the selection stops once post_max_size boxes are kept (= the reference's keep list cut at
+ * post_max_size before the filters: later passes never change earlier kept boxes). di_truncated (B, num_tasks) int32 or NULL:
+ * 1 where the loop stopped with unsuppressed candidates left, written 0 otherwise; di_truncated_sticky (one int32) or NULL: 1 is
+ * ORed into it in that case, never cleared here. di_keep (B * num_tasks, post_max_size) / di_keep_count (B * num_tasks) int32,
+ * both or neither: the kept candidates' ranks in the frame's top-k order and their number, BEFORE the filters (what the
+ * reference returns as `selected`). 3 launches with external keys (+ the merge for num_tasks > 1). */
+size_t sessd_predict_di_workspace_bytes(int batch, int num_tasks, int num_anchors, int pre_max_size, int post_max_size);
+int sessd_predict_di(const float* head, int batch, int num_tasks, int num_pixels, const float* anchors, int anchors_per_frame,
+                     const double* frustum, float score_thresh, int pre_max_size, int post_max_size, float nms_iou_thresh,
+                     const float* post_center_range6, float direction_offset, float* out_box, float* out_score,
+                     int32_t* out_label, int32_t* out_count, int32_t* out_task_count, const unsigned long long* ext_keys,
+                     const int32_t* ext_key_count, float* records, int32_t* record_counts, int capacity_frames, int32_t* cursor,
+                     const sessd_di_cfg_t* di_cfg, int32_t* di_truncated, int32_t* di_truncated_sticky, int32_t* di_keep,
+                     int32_t* di_keep_count, void* workspace, size_t workspace_bytes, sessd_stream_t stream);
 /* spconv.utils.rbbox_iou / rbbox_intersection (third-party spconv v1, imported by det3d/core/bbox/box_np_ops.py:9 for riou_cc /
  * rinter_cc :20-50): pairwise IoU (mode 0) or intersection area (mode 1) of convex quads given as corners (n,4,2) x (k,4,2);
  * pairs whose caller-supplied stand-up IoU is <= standup_thresh stay 0. standup_iou and out are (n,k) row-major. */

@@ -95,4 +95,14 @@ typedef struct {
   float center_range[6];                            /* post_center_range (mg_head_sessd.py:484) */
 } sessd_head_loss_cfg_t;
 
+/* DI-NMS settings of sessd_predict_di: the arguments get_task_detections passes to box_torch_ops.rotate_weighted_nms
+ * (mg_head_sessd.py:1012-1017: centerness_pow 2, nms_cnt_thresh 2.6, intervals (0, 20, 40, 60), sigma squares (0.0009, 0.009,
+ * 0.1, 1), suppressed_thresh 0.3). interval[0 .. n_interval) are the distance bounds, sigma_sq[k] belongs to
+ * [interval[k], interval[k + 1]): n_interval - 1 entries are read. */
+typedef struct {
+  float cnt_thresh, suppressed_thresh, centerness_pow;
+  int32_t n_interval;        /* <= 8 */
+  float interval[8], sigma_sq[8];
+} sessd_di_cfg_t;
+
 #endif

@@ -15,6 +15,9 @@
 //   K4 nms_reduce     greedy walk over the mask (staged in LDS), stops at post_max, fused with
 //   K5 finalize       frustum (float64 planes), direction fix, centre-range mask, ordered compaction, and the frame's
 //                     fixed-size detection record (sessd_predict_fused; the unfused kernels serve pre_max > ~1280)
+// DI-NMS (mg_head_sessd.py:999-1018, the reference's other post-processor; sessd_predict_di) replaces K3 - K5 by di_overlap_rows
+// (dense overlap rows, stand-up prefilter + float64 clipping) and di_select_finalize (centerness damping, the IoU-weighted
+// selection loop, then K5's filters on the averaged boxes and the record): see the comment above those kernels.
 // K1 can also run inside the producer of the head tensor (sessd_ssfa_fuse_head_keys, dense_conv.hip): the keys then arrive
 // with the head and the frame has one launch and one 35 k-thread pass less.
 // Head tensor layout consumed here: planar (B, 22, H*W): ch 0..13 box codes (anchor-major, 7 each),
@@ -25,6 +28,7 @@
 // workspace, and one small launch (merge_tasks_kernel) concatenates them per real frame and writes the record. T = 1 has no
 // such launch and no such rows: the kernels write the caller's outputs as before.
 #include "geom.hpp"
+#include "sessd_hip_types.h"
 
 namespace {
 
@@ -82,7 +86,8 @@ __device__ __forceinline__ void bitonic_sort_lds(unsigned long long* s, int n) {
   }
 }
 
-// Outputs per frame (stride pre_max): cand_box (7), cand_score, cand_dir, corners (8), standup (4), n_top
+// Outputs per frame (stride pre_max): cand_box (7), cand_score, cand_dir, corners (8), standup (4), n_top; cand_ioup / cand_axy (2)
+// only when cand_ioup != nullptr (DI-NMS)
 __global__ __launch_bounds__(SORT_NT) void topk_decode_kernel(const float* __restrict__ head,
                                                                const float* __restrict__ anchors, int anchors_per_frame,
                                                                PostCfg C, const unsigned long long* __restrict__ keys,
@@ -91,7 +96,8 @@ __global__ __launch_bounds__(SORT_NT) void topk_decode_kernel(const float* __res
                                                                int* __restrict__ cand_dir, float* __restrict__ corners,
                                                                float* __restrict__ standup, int* __restrict__ n_top,
                                                                int* __restrict__ rec_cursor, int* __restrict__ rec_base, int batch,
-                                                               int* __restrict__ pair_count) {
+                                                               int* __restrict__ pair_count, float* __restrict__ cand_ioup,
+                                                               float* __restrict__ cand_axy) {
   __shared__ unsigned long long s[SORT_N];
   const int b = blockIdx.x;
   if (threadIdx.x == 0) pair_count[b] = 0;  // the suppression-mask launches that follow append this frame's pairs
@@ -146,6 +152,11 @@ __global__ __launch_bounds__(SORT_NT) void topk_decode_kernel(const float* __res
     cand_score[o] = sc;
     const float d0 = hb[(size_t)(16 + a * 2) * C.num_pix + pix], d1 = hb[(size_t)(17 + a * 2) * C.num_pix + pix];
     cand_dir[o] = d1 > d0 ? 1 : 0;  // torch.max: first maximum on ties
+    if (cand_ioup) {  // DI-NMS only: iou_preds as reassigned at mg_head_sessd.py:971, and the candidate's own anchor centre
+      cand_ioup[o] = (hb[(size_t)(20 + a) * C.num_pix + pix] + 1.0f) * 0.5f;
+      cand_axy[o * 2] = xa;
+      cand_axy[o * 2 + 1] = ya;
+    }
     // boxes_for_nms = box[:, [0,1,3,4,6]] -> corners (box_np_ops.py:512-532) and stand-up box
     const float det[5] = {bx[0], bx[1], bx[3], bx[4], bx[6]};
     float c8[8];
@@ -561,6 +572,296 @@ __global__ __launch_bounds__(256) void copy_counts_kernel(const int* __restrict_
   for (int i = threadIdx.x; i < n; i += 256) dst[i] = src[i];
 }
 
+// ---- DI-NMS (box_torch_ops.rotate_weighted_nms, mg_head_sessd.py:999-1018) as the post-processor of the fused call: the
+// candidates of virtual frame v come from K2 as before (plus iou_pred and the anchor centre), then
+//   di_overlap_rows_kernel     one wave per candidate row i < n_top[v]: stand-up prefilter of the WHOLE row (the core reads
+//                              overlap(A, j) for every j, kept or suppressed, before or after A), zeros stored where it fails,
+//                              the survivors compacted in LDS and clipped in float64 on dense lanes (rounded to float like
+//                              di_overlap_kernel of di_nms.hip). Every entry (i, j), i, j < n_top[v], of the frame's dense
+//                              (pre_max, pre_max) matrix is written each call: no clear launch.
+//   di_select_finalize_kernel  one 1024-thread workgroup per virtual frame, thread j = candidate j: centerness softmax
+//                              (box_torch_ops.py:582-586), normalisation, the sequential loop of nms_cpu.h:173-384 exactly as
+//                              di_select_kernel (di_nms.hip) runs it with centerness_c = 0 -- same picks, same box-order cnt
+//                              sum, same fixed reduction tree -- then finalize_wave on the AVERAGED boxes and the frame's record.
+// Deviations from the reference, both stated in include/sessd_hip.h: the anchors are the task's own (the reference reads task
+// 0's x, y for every task: the same grid in the KITTI configs), and the loop stops once post_max boxes are kept (the reference
+// wrapper ignores post_max_size; later passes cannot change earlier kept boxes, so this is its keep list cut at post_max).
+// A pair's stand-up IoU > 0 test of the suppression rule is implied: overlap > 0 is only ever stored where the prefilter passed.
+struct DiCfg {
+  float cnt_thresh, suppressed_thresh, centerness_pow;
+  int n_interval;
+  float interval[8], sigma_sq[8];
+};
+
+constexpr int DI_ROWS = 4;     // waves (rows) per workgroup of the overlap kernel
+constexpr int DI_MAXN = 1024;  // candidates: one thread each in the selection workgroup
+
+__global__ __launch_bounds__(DI_ROWS * 64) void di_overlap_rows_kernel(const int* __restrict__ n_top, int pre_max,
+                                                                        const float* __restrict__ corners,
+                                                                        const float* __restrict__ standup,
+                                                                        float* __restrict__ overlap) {
+  __shared__ unsigned short s_list[DI_ROWS][DI_MAXN];
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int i = blockIdx.x * DI_ROWS + wv;
+  const int n = min(n_top[b], pre_max);
+  if (i >= n) return;  // no workgroup barrier below
+  const float* cb = corners + (size_t)b * pre_max * 8;
+  const float4* sb = reinterpret_cast<const float4*>(standup + (size_t)b * pre_max * 4);
+  const float4 s4 = sb[i];
+  const float si[4] = {s4.x, s4.y, s4.z, s4.w};
+  float* row = overlap + ((size_t)b * pre_max + i) * pre_max;
+  int total = 0;
+  for (int j0 = 0; j0 < n; j0 += 64) {
+    const int j = j0 + lane;
+    bool pass = false;
+    if (j < n) {
+      const float4 t4 = sb[j];
+      const float sj[4] = {t4.x, t4.y, t4.z, t4.w};
+      pass = rnms_prefilter(si, sj);
+      if (!pass) row[j] = 0.f;
+    }
+    const unsigned long long bal = __ballot(pass);
+    if (pass) s_list[wv][total + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned short)j;
+    total += __popcll(bal);
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the list is read by other lanes of this wave
+  const float4* c4 = reinterpret_cast<const float4*>(cb + (size_t)i * 8);
+  const float4 a4 = c4[0], b4 = c4[1];
+  const float ci[8] = {a4.x, a4.y, a4.z, a4.w, b4.x, b4.y, b4.z, b4.w};
+  double px[4], py[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) { px[q] = ci[2 * q]; py[q] = ci[2 * q + 1]; }
+  const double area_i = fabs(sessd_poly_area2(px, py, 4)) * 0.5;
+  for (int p = lane; p < total; p += 64) {
+    const int j = s_list[wv][p];
+    const float4* d4 = reinterpret_cast<const float4*>(cb + (size_t)j * 8);
+    const float4 e4 = d4[0], f4 = d4[1];
+    const float cj[8] = {e4.x, e4.y, e4.z, e4.w, f4.x, f4.y, f4.z, f4.w};
+    float v = 0.f;
+    const double inter = sessd_quad_inter_area_green(ci, cj);
+    if (inter > 0) {
+      double qx[4], qy[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { qx[q] = cj[2 * q]; qy[q] = cj[2 * q + 1]; }
+      const float ia = (float)inter;
+      const float ua = (float)(area_i + fabs(sessd_poly_area2(qx, qy, 4)) * 0.5 - inter);
+      v = ua > 0.f ? ia / ua : 0.f;
+    }
+    row[j] = v;
+  }
+}
+
+__device__ __forceinline__ float di_wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Dynamic LDS: keep[kcap] (the identity list finalize_wave walks) | rec[kcap * 9], kcap = min(post_max, pre_max).
+// di_box / di_score / di_dir: the kept boxes of the frame, stride pre_max like the candidates (finalize_wave's indexing).
+__global__ __launch_bounds__(DI_MAXN) void di_select_finalize_kernel(
+    PostCfg C, DiCfg D, const int* __restrict__ n_top, const float* __restrict__ overlap, const float* __restrict__ cand_box,
+    const float* __restrict__ cand_score, const int* __restrict__ cand_dir, const float* __restrict__ cand_ioup,
+    const float* __restrict__ cand_axy, float* di_box, float* di_score, int* di_dir, const double* __restrict__ frustum,
+    float* __restrict__ out_box, float* __restrict__ out_score, int* __restrict__ out_label, int* __restrict__ out_count,
+    int* __restrict__ di_truncated, int* __restrict__ di_sticky, int* __restrict__ di_keep, int* __restrict__ di_keep_count,
+    float* __restrict__ records, int* __restrict__ rec_count, int capacity, const int* __restrict__ rec_base) {
+  extern __shared__ __attribute__((aligned(16))) int s_dyn[];
+  __shared__ float s_red[16][10];
+  __shared__ unsigned long long s_key[16];
+  __shared__ float s_bc[12];
+  __shared__ float s_terms[DI_MAXN];  // the pass's non-zero cnt terms in box order
+  __shared__ int s_nz[16];
+  __shared__ int s_written;
+  const int v = blockIdx.x;
+  const int j = threadIdx.x, lane = j & 63, wv = j >> 6;
+  const int n = min(n_top[v], C.pre_max);
+  const bool live = j < n;
+  const size_t vb = (size_t)v * C.pre_max;
+  const int kcap = min(C.post_max, C.pre_max);
+  int* s_keep = s_dyn;
+  float* s_rec = reinterpret_cast<float*>(s_dyn + kcap);
+  float my_box[7];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) my_box[k] = live ? cand_box[(vb + j) * 7 + k] : 0.f;
+  const float my_ioup = live ? cand_ioup[vb + j] : 0.f;
+  // ---- centerness damping (box_torch_ops.py:582-586): score *= (1 - softmax(|xy - anchor xy|))^pow, float32, max subtracted
+  float my_score = live ? cand_score[vb + j] : 0.f;
+  {
+    float d = -3.0e38f;
+    if (live) {
+      const float dx = fabsf(my_box[0] - cand_axy[(vb + j) * 2]), dy = fabsf(my_box[1] - cand_axy[(vb + j) * 2 + 1]);
+      d = __fsqrt_rn(dx * dx + dy * dy);
+    }
+    float m = d;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if (lane == 0) s_red[wv][0] = m;
+    __syncthreads();
+    float dmax = s_red[0][0];
+    for (int w = 1; w < 16; ++w) dmax = fmaxf(dmax, s_red[w][0]);
+    __syncthreads();
+    const float e = live ? expf(d - dmax) : 0.f;
+    const float t = di_wave_sum(e);
+    if (lane == 0) s_red[wv][0] = t;
+    __syncthreads();
+    float sum = 0.f;
+    for (int w = 0; w < 16; ++w) sum += s_red[w][0];
+    __syncthreads();
+    if (live) {
+      const float damp = 1.0f - e / sum;
+      my_score *= D.centerness_pow == 2.0f ? damp * damp : powf(damp, D.centerness_pow);
+    }
+  }
+  // ---- normalised scores (nms_cpu.h:233-262)
+  float srw = my_score;
+  {
+    float m = live ? srw : -10000.f;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if (lane == 0) s_red[wv][0] = m;
+    __syncthreads();
+    float mx = -10000.f;
+    for (int w = 0; w < 16; ++w) mx = fmaxf(mx, s_red[w][0]);
+    __syncthreads();
+    if (j == 0) s_bc[11] = mx;
+    srw /= mx;
+  }
+  bool suppressed = !live;
+  int nkeep = 0;
+  int truncated = 0;
+  __syncthreads();
+  const float score_max4norm = s_bc[11];
+  for (;;) {
+    const bool cand = !suppressed && my_score > -1.f;
+    if (nkeep >= C.post_max) {  // uniform: the outputs hold post_max rows per task
+      truncated = __syncthreads_or(cand ? 1 : 0);
+      break;
+    }
+    // ---- the unsuppressed box with the largest (damped) score, lowest index on ties
+    unsigned long long key = 0ull;
+    if (cand) {
+      unsigned u = __float_as_uint(my_score);
+      u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+      key = ((unsigned long long)u << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)j);
+    }
+    if (__ballot(cand)) {  // wave-uniform: a wave without candidates keeps key 0 (the maximum of zeros)
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(key, o, 64);
+        key = other > key ? other : key;
+      }
+    }
+    if (lane == 0) s_key[wv] = key;
+    __syncthreads();
+    unsigned long long best = 0ull;
+    for (int w = 0; w < 16; ++w) best = s_key[w] > best ? s_key[w] : best;
+    if (best == 0ull) break;  // everything suppressed (uniform)
+    const int idx = (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull));  // < n: only live threads make keys
+    if (j == idx) suppressed = true;
+    const float bx = cand_box[(vb + idx) * 7], by = cand_box[(vb + idx) * 7 + 1];
+    const float dist2origin = (float)sqrt((double)bx * bx + (double)by * by);
+    // ---- this box's contribution (one class per task: every candidate of the frame carries A's label)
+    float cnt = 0.f, wsum = 0.f, avg[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sbox = -1.f;
+    bool newly = false, weighs = false;
+    if (live) {
+      const float ov = overlap[(vb + idx) * C.pre_max + j];
+      if (ov > 0.f) {
+        cnt = ov * my_ioup;
+        if (ov > D.suppressed_thresh) {
+          weighs = true;
+          sbox = srw;
+          float w = 0.f;
+          for (int k = 0; k + 1 < D.n_interval; ++k)
+            if (dist2origin >= D.interval[k] && dist2origin < D.interval[k + 1]) {
+              const double dd = 1.0 - (double)ov;
+              w = (float)exp(-(dd * dd) / (double)D.sigma_sq[k]);
+            }
+          wsum = w * my_ioup;
+#pragma unroll
+          for (int k = 0; k < 7; ++k) avg[k] = w * my_ioup * my_box[k];
+        }
+        if (!suppressed && ov >= D.suppressed_thresh) {
+          suppressed = true;
+          newly = true;
+        }
+      }
+    }
+    // ---- cnt in the reference's order (box 0, 1, 2, ... in float32), the other sums in the fixed tree: see di_select_kernel
+    const float cnt_term = cnt;
+    const unsigned long long nzb = __ballot(cnt_term != 0.f);
+    if (__ballot(weighs)) {  // wave-uniform: in a wave without a weighing box every lane already holds the tree's result (0 / -1)
+      wsum = di_wave_sum(wsum);
+#pragma unroll
+      for (int k = 0; k < 7; ++k) avg[k] = di_wave_sum(avg[k]);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) sbox = fmaxf(sbox, __shfl_xor(sbox, o, 64));
+    }
+    __syncthreads();  // s_key / s_red of the previous pass are no longer read
+    if (lane == 0) {
+      s_red[wv][1] = wsum; s_red[wv][9] = sbox;
+#pragma unroll
+      for (int k = 0; k < 7; ++k) s_red[wv][2 + k] = avg[k];
+      s_nz[wv] = __popcll(nzb);
+    }
+    __syncthreads();
+    if (cnt_term != 0.f) {
+      int off = 0;
+      for (int w = 0; w < wv; ++w) off += s_nz[w];
+      s_terms[off + __popcll(nzb & ((1ull << lane) - 1ull))] = cnt_term;
+    }
+    if (j >= 1 && j < 10) {
+      float r = s_red[0][j];
+      for (int w = 1; w < 16; ++w) r = (j == 9) ? fmaxf(r, s_red[w][j]) : r + s_red[w][j];
+      s_bc[j] = r;
+    }
+    __syncthreads();
+    if (j == 0) {
+      int total = 0;
+      for (int w = 0; w < 16; ++w) total += s_nz[w];
+      float c = 0.f;
+      for (int t = 0; t < total; ++t) c += s_terms[t];
+      s_bc[0] = c;
+    }
+    __syncthreads();
+    const bool kept = s_bc[0] > D.cnt_thresh;
+    if (kept) {  // nkeep < post_max and nkeep < n <= pre_max: inside the frame's rows
+      if (j == 0) {
+        di_score[vb + nkeep] = s_bc[9] * score_max4norm;
+        di_dir[vb + nkeep] = cand_dir[vb + idx];
+        if (di_keep) di_keep[(size_t)v * C.post_max + nkeep] = idx;
+      }
+      if (j < 7) di_box[(vb + nkeep) * 7 + j] = s_bc[2 + j] / s_bc[1];
+      ++nkeep;
+    } else if (newly) {
+      suppressed = false;  // the boxes this pass suppressed come back; A itself stays marked
+    }
+    __syncthreads();
+  }
+  // ---- after the core (mg_head_sessd.py:1024-1045): frustum, direction fix, range mask on the averaged boxes, then the record
+  for (int k = j; k < nkeep; k += DI_MAXN) s_keep[k] = k;
+  __syncthreads();  // the kept rows (global) and the list (LDS) are visible to wave 0
+  if (j < 64) {
+    const int written = finalize_wave(C, v, j, s_keep, nkeep, di_box, di_score, di_dir, frustum, out_box, out_score, out_label,
+                                      records ? s_rec : nullptr);
+    if (j == 0) {
+      out_count[v] = written;
+      s_written = written;
+      if (di_truncated) di_truncated[v] = truncated;
+      if (di_sticky && truncated) atomicOr(di_sticky, 1);
+      if (di_keep_count) di_keep_count[v] = nkeep;
+    }
+  }
+  if (!records) return;
+  __syncthreads();
+  const int written = s_written;
+  const int slot = (rec_base[0] + v) % capacity;
+  float* dst = records + (size_t)slot * C.post_max * 9;
+  for (int e = j; e < C.post_max * 9; e += DI_MAXN) dst[e] = e < written * 9 ? s_rec[e] : 0.f;
+  if (j == 0) rec_count[slot] = written;
+}
+
 struct PostWs {
   unsigned long long* keys;
   int* count;
@@ -581,10 +882,17 @@ struct PostWs {
   float* task_score;
   int* task_label;
   int* task_count;
+  // DI-NMS only (instead of mask / keep / pairs): K2's extra candidate values, the dense overlap matrices, the kept boxes
+  float* cand_ioup;
+  float* cand_axy;
+  float* overlap;
+  float* di_box;
+  float* di_score;
+  int* di_dir;
 };
 
 // batch = virtual frames (B * num_tasks); the single-task layout is unchanged
-size_t post_ws_layout(int batch, int num_tasks, int num_anchors, int pre_max, int post_max, PostWs* w, char* base) {
+size_t post_ws_layout(int batch, int num_tasks, int num_anchors, int pre_max, int post_max, PostWs* w, char* base, bool di = false) {
   size_t off = 0;
   auto take = [&](size_t bytes) {
     size_t o = off;
@@ -600,11 +908,11 @@ size_t post_ws_layout(int batch, int num_tasks, int num_anchors, int pre_max, in
   size_t o_cor = take((size_t)batch * pre_max * 8 * 4);
   size_t o_su = take((size_t)batch * pre_max * 4 * 4);
   size_t o_nt = take((size_t)batch * 4);
-  size_t o_mask = take((size_t)batch * pre_max * words * 8);
-  size_t o_keep = take((size_t)batch * post_max * 4);
+  size_t o_mask = take(di ? 0 : (size_t)batch * pre_max * words * 8);
+  size_t o_keep = take(di ? 0 : (size_t)batch * post_max * 4);
   size_t o_nk = take((size_t)batch * 4);
   size_t o_rb = take(4);
-  size_t o_pairs = take((size_t)batch * rn_pair_cap(pre_max) * 4);
+  size_t o_pairs = take(di ? 0 : (size_t)batch * rn_pair_cap(pre_max) * 4);
   size_t o_pc = take((size_t)batch * 4);
   size_t o_tb = 0, o_ts = 0, o_tl = 0, o_tc = 0;
   if (num_tasks > 1) {
@@ -612,6 +920,15 @@ size_t post_ws_layout(int batch, int num_tasks, int num_anchors, int pre_max, in
     o_ts = take((size_t)batch * post_max * 4);
     o_tl = take((size_t)batch * post_max * 4);
     o_tc = take((size_t)batch * 4);
+  }
+  size_t o_ip = 0, o_ax = 0, o_ov = 0, o_db = 0, o_ds = 0, o_dd = 0;
+  if (di) {
+    o_ip = take((size_t)batch * pre_max * 4);
+    o_ax = take((size_t)batch * pre_max * 2 * 4);
+    o_ov = take((size_t)batch * pre_max * pre_max * 4);
+    o_db = take((size_t)batch * pre_max * 7 * 4);
+    o_ds = take((size_t)batch * pre_max * 4);
+    o_dd = take((size_t)batch * pre_max * 4);
   }
   if (w) {
     w->keys = (unsigned long long*)(base + o_keys);
@@ -632,6 +949,12 @@ size_t post_ws_layout(int batch, int num_tasks, int num_anchors, int pre_max, in
     w->task_score = (float*)(base + o_ts);
     w->task_label = (int*)(base + o_tl);
     w->task_count = (int*)(base + o_tc);
+    w->cand_ioup = (float*)(base + o_ip);
+    w->cand_axy = (float*)(base + o_ax);
+    w->overlap = (float*)(base + o_ov);
+    w->di_box = (float*)(base + o_db);
+    w->di_score = (float*)(base + o_ds);
+    w->di_dir = (int*)(base + o_dd);
   }
   return off;
 }
@@ -697,13 +1020,17 @@ size_t sessd_predict_workspace_bytes(int batch, int num_anchors, int pre_max_siz
 // rule: slot = (*cursor + b) % capacity_frames, *cursor += batch) from inside the last launch.
 // T = 1: 3 launches per call with external keys and pre_max_size such that the suppression mask fits the LDS (<= ~1280): top-k
 // + decode, suppression mask, greedy walk + filters + record. T > 1: the same launches over B*T virtual frames + the merge.
-int sessd_predict_tasks(const float* head, int batch, int num_tasks, int num_pixels, const float* anchors, int anchors_per_frame,
+// di != nullptr: DI-NMS (sessd_predict_di) instead of the suppression mask and the greedy walk; everything else is shared
+static int predict_impl(const float* head, int batch, int num_tasks, int num_pixels, const float* anchors, int anchors_per_frame,
                         const double* frustum, float score_thresh, int pre_max_size, int post_max_size, float nms_iou_thresh,
                         const float* post_center_range6, float direction_offset, float* out_box, float* out_score,
                         int* out_label, int* out_count, int* out_task_count, const unsigned long long* ext_keys,
                         const int* ext_key_count, float* records, int* record_counts, int capacity_frames, int* cursor,
+                        const DiCfg* di, int* di_truncated, int* di_truncated_sticky, int* di_keep, int* di_keep_count,
                         void* workspace, size_t workspace_bytes, hipStream_t stream) {
   if (batch < 1 || num_pixels < 1 || pre_max_size < 1 || pre_max_size > 4096 || post_max_size < 1) return SESSD_EINVAL;
+  if (di && pre_max_size > DI_MAXN) return SESSD_EINVAL;  // one thread per candidate in the selection workgroup
+  if ((di_keep == nullptr) != (di_keep_count == nullptr)) return SESSD_EINVAL;
   if (num_tasks < 1 || num_tasks > 4) return SESSD_EINVAL;
   if (pre_max_size > SORT_N - 64) return SESSD_EINVAL;  // running top-k keeps pre_max + a fresh chunk in 2048 slots
   if ((ext_keys == nullptr) != (ext_key_count == nullptr)) return SESSD_EINVAL;
@@ -713,7 +1040,7 @@ int sessd_predict_tasks(const float* head, int batch, int num_tasks, int num_pix
   const bool multi = num_tasks > 1;
   const int vbatch = batch * num_tasks;  // virtual frames
   PostWs w;
-  if (post_ws_layout(vbatch, num_tasks, A, pre_max_size, post_max_size, &w, (char*)workspace) > workspace_bytes)
+  if (post_ws_layout(vbatch, num_tasks, A, pre_max_size, post_max_size, &w, (char*)workspace, di != nullptr) > workspace_bytes)
     return SESSD_EWORKSPACE;
   PostCfg C;
   C.num_pix = num_pixels;
@@ -736,10 +1063,11 @@ int sessd_predict_tasks(const float* head, int batch, int num_tasks, int num_pix
   }
   SESSD_LAUNCH(topk_decode_kernel, dim3(vbatch), dim3(SORT_NT), 0, stream, head, anchors, anchors_per_frame, C,
                      keys, A, key_count, w.cand_box, w.cand_score, w.cand_dir, w.corners, w.standup, w.n_top,
-                     records ? cursor : (int*)nullptr, w.rec_base, batch, w.pair_count);
+                     records ? cursor : (int*)nullptr, w.rec_base, batch, w.pair_count, di ? w.cand_ioup : (float*)nullptr,
+                     di ? w.cand_axy : (float*)nullptr);
   SESSD_CHECK_LAUNCH();
   const int words = sessd_divup(pre_max_size, 64);
-  {
+  if (!di) {
     const int rc = launch_rnms_mask(w.n_top, vbatch, pre_max_size, nms_iou_thresh, w.corners, w.standup, w.mask, words, w.pairs,
                                     w.pair_count, stream);
     if (rc != SESSD_OK) return rc;
@@ -751,7 +1079,17 @@ int sessd_predict_tasks(const float* head, int batch, int num_tasks, int num_pix
   int* k_count = multi ? w.task_count : out_count;
   float* k_records = multi ? nullptr : records;
   const size_t lds = (size_t)pre_max_size * words * 8 + (size_t)post_max_size * 4 + (size_t)post_max_size * 9 * 4;
-  if (lds <= 160 * 1024 - 1024) {
+  if (di) {
+    SESSD_LAUNCH(di_overlap_rows_kernel, dim3(sessd_divup(pre_max_size, DI_ROWS), vbatch), dim3(DI_ROWS * 64), 0, stream, w.n_top,
+                 pre_max_size, w.corners, w.standup, w.overlap);
+    SESSD_CHECK_LAUNCH();
+    const int kcap = post_max_size < pre_max_size ? post_max_size : pre_max_size;
+    SESSD_LAUNCH(di_select_finalize_kernel, dim3(vbatch), dim3(DI_MAXN), (size_t)kcap * 10 * 4, stream, C, *di, w.n_top, w.overlap,
+                 w.cand_box, w.cand_score, w.cand_dir, w.cand_ioup, w.cand_axy, w.di_box, w.di_score, w.di_dir, frustum, k_box,
+                 k_score, k_label, k_count, di_truncated, di_truncated_sticky, di_keep, di_keep_count, k_records, record_counts,
+                 capacity_frames, w.rec_base);
+    SESSD_CHECK_LAUNCH();
+  } else if (lds <= 160 * 1024 - 1024) {
     static bool attr_set = false;
     if (!attr_set) {
       SESSD_TRY(hipFuncSetAttribute((const void*)nms_reduce_finalize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -785,6 +1123,50 @@ int sessd_predict_tasks(const float* head, int batch, int num_tasks, int num_pix
     SESSD_CHECK_LAUNCH();
   }
   return SESSD_OK;
+}
+
+int sessd_predict_tasks(const float* head, int batch, int num_tasks, int num_pixels, const float* anchors, int anchors_per_frame,
+                        const double* frustum, float score_thresh, int pre_max_size, int post_max_size, float nms_iou_thresh,
+                        const float* post_center_range6, float direction_offset, float* out_box, float* out_score,
+                        int* out_label, int* out_count, int* out_task_count, const unsigned long long* ext_keys,
+                        const int* ext_key_count, float* records, int* record_counts, int capacity_frames, int* cursor,
+                        void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return predict_impl(head, batch, num_tasks, num_pixels, anchors, anchors_per_frame, frustum, score_thresh, pre_max_size,
+                      post_max_size, nms_iou_thresh, post_center_range6, direction_offset, out_box, out_score, out_label, out_count,
+                      out_task_count, ext_keys, ext_key_count, records, record_counts, capacity_frames, cursor, nullptr, nullptr,
+                      nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+size_t sessd_predict_di_workspace_bytes(int batch, int num_tasks, int num_anchors, int pre_max_size, int post_max_size) {
+  if (batch < 1 || num_tasks < 1 || num_tasks > 4 || pre_max_size < 1 || pre_max_size > DI_MAXN) return 0;
+  return post_ws_layout(batch * num_tasks, num_tasks, num_anchors, pre_max_size, post_max_size, nullptr, nullptr, true);
+}
+
+// sessd_predict_tasks with DI-NMS (box_torch_ops.rotate_weighted_nms, enable_centerness=True, centerness_c=False) as the
+// post-processor of every (frame, task): see the kernels above and include/sessd_hip.h. nms_iou_thresh is accepted and never read,
+// as in the reference. 3 launches per call with external keys (top-k + decode, overlap rows, selection + filters + record), one
+// fewer than the greedy path; T > 1 adds the merge.
+int sessd_predict_di(const float* head, int batch, int num_tasks, int num_pixels, const float* anchors, int anchors_per_frame,
+                     const double* frustum, float score_thresh, int pre_max_size, int post_max_size, float nms_iou_thresh,
+                     const float* post_center_range6, float direction_offset, float* out_box, float* out_score, int* out_label,
+                     int* out_count, int* out_task_count, const unsigned long long* ext_keys, const int* ext_key_count,
+                     float* records, int* record_counts, int capacity_frames, int* cursor, const sessd_di_cfg_t* di_cfg,
+                     int* di_truncated, int* di_truncated_sticky, int* di_keep, int* di_keep_count, void* workspace,
+                     size_t workspace_bytes, hipStream_t stream) {
+  if (!di_cfg || di_cfg->n_interval < 0 || di_cfg->n_interval > 8) return SESSD_EINVAL;
+  DiCfg D;
+  D.cnt_thresh = di_cfg->cnt_thresh;
+  D.suppressed_thresh = di_cfg->suppressed_thresh;
+  D.centerness_pow = di_cfg->centerness_pow;
+  D.n_interval = di_cfg->n_interval;
+  for (int k = 0; k < 8; ++k) {
+    D.interval[k] = k < D.n_interval ? di_cfg->interval[k] : 0.f;
+    D.sigma_sq[k] = k + 1 < D.n_interval ? di_cfg->sigma_sq[k] : 1.f;
+  }
+  return predict_impl(head, batch, num_tasks, num_pixels, anchors, anchors_per_frame, frustum, score_thresh, pre_max_size,
+                      post_max_size, nms_iou_thresh, post_center_range6, direction_offset, out_box, out_score, out_label, out_count,
+                      out_task_count, ext_keys, ext_key_count, records, record_counts, capacity_frames, cursor, &D, di_truncated,
+                      di_truncated_sticky, di_keep, di_keep_count, workspace, workspace_bytes, stream);
 }
 
 int sessd_predict_fused(const float* head, int batch, int num_pixels, const float* anchors, int anchors_per_frame,

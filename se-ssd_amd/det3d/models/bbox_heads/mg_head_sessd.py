@@ -434,9 +434,11 @@ class MultiGroupHead(nn.Module):
         if calib is not None and "frustum" in calib:
             frustum = calib["frustum"].to(head.device).double().contiguous()
         nms = test_cfg["nms"] if isinstance(test_cfg, dict) else test_cfg.nms
+        # nms_type "rotate_weighted_nms": DI-NMS, the other branch of get_task_detections (mg_head_sessd.py:999-1018)
+        nms_type, di = ops.nms_settings(nms, int(nms["nms_pre_max_size"]))
         out = ops.predict(head, anc, frustum, float(self.thresh), int(nms["nms_pre_max_size"]),
                           int(nms["nms_post_max_size"]), float(nms["nms_iou_threshold"]), self.post_center_range,
-                          float(self.direction_offset), num_tasks=T)
+                          float(self.direction_offset), num_tasks=T, nms_type=nms_type, di=di)
         counts = out["count"].cpu().tolist()  # the single host read of the whole predict path
         meta = example.get("metadata", [None] * B)
         ret = []

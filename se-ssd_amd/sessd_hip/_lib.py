@@ -49,6 +49,12 @@ class HeadLossCfg(C.Structure):
                 ("direction_offset", f32), ("score_thresh", f32), ("match_iou_thresh", f32), ("center_range", f32 * 6)]
 
 
+class DiCfg(C.Structure):
+    """sessd_di_cfg_t (include/sessd_hip_types.h)"""
+    _fields_ = [("cnt_thresh", f32), ("suppressed_thresh", f32), ("centerness_pow", f32), ("n_interval", i32),
+                ("interval", f32 * 8), ("sigma_sq", f32 * 8)]
+
+
 # name -> (restype, argtypes). Kept in step with include/sessd_hip.h (tests/test_abi.py checks it).
 SIGNATURES = {
     "sessd_version": (C.c_char_p, []),
@@ -121,6 +127,9 @@ SIGNATURES = {
     "sessd_predict_tasks_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "sessd_predict_tasks": (i32, [vp, i32, i32, i32, vp, i32, vp, f32, i32, i32, f32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp,
                                   sz, vp]),
+    "sessd_predict_di_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "sessd_predict_di": (i32, [vp, i32, i32, i32, vp, i32, vp, f32, i32, i32, f32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp,
+                               vp, vp, vp, vp, vp, sz, vp]),
     "sessd_di_nms_workspace_bytes": (sz, [i32]),
     "sessd_di_nms": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, f32, vp, i32, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "sessd_pack_detections": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp]),

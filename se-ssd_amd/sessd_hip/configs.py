@@ -51,6 +51,11 @@ TEST_CFG = dict(nms=dict(use_rotate_nms=True, use_multi_class_nms=False, nms_pre
                          nms_iou_threshold=0.01),
                 score_threshold=0.3, post_center_limit_range=[0, -40.0, -5.0, 70.4, 40.0, 5.0], max_per_img=100)
 
+# TEST_CFG with the other post-processor of get_task_detections (mg_head_sessd.py:999-1018): DI-NMS. Further keys of "nms" it
+# reads, defaults = the reference's literals: nms_cnt_thresh, nms_sigma_dist_interval, nms_sigma_square, suppressed_thresh,
+# centerness_pow (sessd_hip.ops.DI_DEFAULTS).
+TEST_CFG_DI_NMS = dict(TEST_CFG, nms=dict(TEST_CFG["nms"], nms_type="rotate_weighted_nms"))
+
 VOXEL_GENERATOR = dict(range=[0, -40.0, -3.0, 70.4, 40.0, 1.0], voxel_size=[0.05, 0.05, 0.1], max_points_in_voxel=5,
                        max_voxel_num=20000)
 

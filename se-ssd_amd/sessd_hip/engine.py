@@ -182,6 +182,11 @@ class InferenceEngine:
         sort_sites: renumber the voxels by grid row between the voxelizer and the first sparse conv
         (sessd_sparse_renumber_sites; validated on hardware in round 2, tests/test_site_renumber_gpu.py); the detections do
         not depend on it."""
+        # the post-processor (test_cfg["nms"]["nms_type"]: the greedy rotated NMS, or DI-NMS = "rotate_weighted_nms"), checked
+        # before anything touches the device
+        nms = test_cfg["nms"] if isinstance(test_cfg, dict) else test_cfg.nms
+        self.nms_type, self.di = ops.nms_settings(nms, int(nms["nms_pre_max_size"]))
+        self.di_cfg = ops.check_di(self.di) if self.di is not None else None
         self.dev = torch.device("cuda:0") if device is None else device
         dev = self.dev
         self.B = int(batch_size)
@@ -329,8 +334,14 @@ class InferenceEngine:
                         count=torch.zeros((B,), dtype=i32, device=dev))
         if T > 1:
             self.out["task_count"] = torch.zeros((B, T), dtype=i32, device=dev)
-        self.pred_ws = torch.empty(int(lib.sessd_predict_tasks_workspace_bytes(B, T, 2 * H * W, self.pre_max, self.post_max)),
-                                   dtype=torch.uint8, device=dev)
+        ws_bytes = lib.sessd_predict_tasks_workspace_bytes if self.di_cfg is None else lib.sessd_predict_di_workspace_bytes
+        self.pred_ws = torch.empty(int(ws_bytes(B, T, 2 * H * W, self.pre_max, self.post_max)), dtype=torch.uint8, device=dev)
+        # DI-NMS keeps at most post_max boxes per (frame, task) (the reference's wrapper has no cap): di_truncated (B, T) says where
+        # the selection stopped with candidates left, nms_truncated is the STICKY OR over all frames so far (outside every per-frame
+        # clear, like self.err; nothing raises on it)
+        self.nms_truncated = torch.zeros((1,), dtype=i32, device=dev)
+        if self.di_cfg is not None:
+            self.out["di_truncated"] = torch.zeros((B, T), dtype=i32, device=dev)
         self.keys = torch.empty((B * T, 2 * H * W), dtype=torch.int64, device=dev)  # score-filter keys written by the head launch
         self.fuse_predict = True  # score filter inside the head launch; NMS walk + filters + record in one launch
         self.batched_voxelizer = True  # the frames of a batch in four launches (False: four per frame, as round 3)
@@ -1073,6 +1084,21 @@ class InferenceEngine:
         # ---- predict (a11-a14): top-k + decode, suppression mask, greedy walk + filters (+ the frame's record): 3 launches
         use_keys = fused_keys and self.fuse_predict
         rec = self.records is not None
+        if self.di_cfg is not None:  # DI-NMS: top-k + decode, overlap rows, selection + filters (+ record) (+ the merge for T > 1)
+            import ctypes
+            check(lib.sessd_predict_di(self.head.data_ptr(), B, self.num_tasks, self.H * self.W, self.anchors.data_ptr(), 0,
+                                       0 if self.frustum is None else self.frustum.data_ptr(), self.score_thresh, self.pre_max,
+                                       self.post_max, self.nms_thresh, self.post_range.data_ptr(), self.dir_offset,
+                                       self.out["box"].data_ptr(), self.out["score"].data_ptr(), self.out["label"].data_ptr(),
+                                       self.out["count"].data_ptr(), self.out["task_count"].data_ptr() if self.num_tasks > 1 else 0,
+                                       self.keys.data_ptr() if use_keys else 0, self.key_count.data_ptr() if use_keys else 0,
+                                       self.records.data_ptr() if rec else 0, self.record_counts.data_ptr() if rec else 0,
+                                       self.records.shape[0] if rec else 0, self.record_cursor.data_ptr() if rec else 0,
+                                       ctypes.addressof(self.di_cfg), self.out["di_truncated"].data_ptr(),
+                                       self.nms_truncated.data_ptr(), 0, 0, self.pred_ws.data_ptr(), self.pred_ws.numel(), s),
+                  "predict_di")
+            self._mark("predict")
+            return self.out
         if self.num_tasks > 1:  # the same launches over B * T virtual frames + the merge in task order
             check(lib.sessd_predict_tasks(self.head.data_ptr(), B, self.num_tasks, self.H * self.W, self.anchors.data_ptr(), 0,
                                           0 if self.frustum is None else self.frustum.data_ptr(), self.score_thresh, self.pre_max,

@@ -2222,9 +2222,56 @@ def fill_multi(segments):
 
 
 # ------------------------------------------------------------------ predict / post-processing
+NMS_TYPES = ("rotate_nms", "rotate_weighted_nms")
+DI_MAX_CANDIDATES = 1024   # sessd_predict_di: one thread per candidate in the selection workgroup
+# the literals get_task_detections passes to rotate_weighted_nms (mg_head_sessd.py:1012-1017)
+DI_DEFAULTS = dict(nms_cnt_thresh=2.6, nms_sigma_dist_interval=(0, 20, 40, 60), nms_sigma_square=(0.0009, 0.009, 0.1, 1),
+                   suppressed_thresh=0.3, centerness_pow=2)
+
+
+def nms_settings(nms_cfg, pre_max=None):
+    """(nms_type, di) of a test_cfg["nms"] mapping: nms_type absent = "rotate_nms" (di None); "rotate_weighted_nms" = DI-NMS with
+    DI_DEFAULTS overridden by the keys the mapping carries. Raises ValueError for an unknown nms_type, for pre_max above the
+    1024 candidates DI-NMS handles and for malformed intervals -- before anything touches the device."""
+    get = nms_cfg.get if hasattr(nms_cfg, "get") else (lambda k, d=None: getattr(nms_cfg, k, d))
+    nms_type = get("nms_type", None)
+    nms_type = "rotate_nms" if nms_type is None else nms_type
+    if nms_type not in NMS_TYPES:
+        raise ValueError("nms_type must be one of %s, got %r" % (NMS_TYPES, nms_type))
+    if nms_type == "rotate_nms":
+        return nms_type, None
+    di = {k: (get(k, None) if get(k, None) is not None else d) for k, d in DI_DEFAULTS.items()}
+    check_di(di, pre_max)
+    return nms_type, di
+
+
+def check_di(di, pre_max=None):
+    """DI-NMS settings -> the sessd_di_cfg_t of the call (ValueError for what the kernels do not cover)."""
+    from ._lib import DiCfg
+    unknown = set(di) - set(DI_DEFAULTS)
+    if unknown:
+        raise ValueError("unknown DI-NMS settings %s (known: %s)" % (sorted(unknown), sorted(DI_DEFAULTS)))
+    d = dict(DI_DEFAULTS)
+    d.update(di)
+    if pre_max is not None and int(pre_max) > DI_MAX_CANDIDATES:
+        raise ValueError("rotate_weighted_nms handles at most %d candidates per (frame, task) (one thread each in the selection "
+                         "workgroup): nms_pre_max_size = %d" % (DI_MAX_CANDIDATES, int(pre_max)))
+    iv, sg = [float(v) for v in d["nms_sigma_dist_interval"]], [float(v) for v in d["nms_sigma_square"]]
+    if not 1 <= len(iv) <= 8 or len(sg) < len(iv) - 1:
+        raise ValueError("DI-NMS takes 1 to 8 distance bounds and one sigma square per interval, got %d and %d" % (len(iv), len(sg)))
+    c = DiCfg()
+    c.cnt_thresh, c.suppressed_thresh, c.centerness_pow = float(d["nms_cnt_thresh"]), float(d["suppressed_thresh"]), float(d["centerness_pow"])
+    c.n_interval = len(iv)
+    for k, v in enumerate(iv):
+        c.interval[k] = v
+    for k, v in enumerate(sg[:8]):
+        c.sigma_sq[k] = v
+    return c
+
+
 def predict(head, anchors, frustum=None, score_thresh=0.3, pre_max=1000, post_max=100, nms_thresh=0.01,
             post_center_range=(0, -40.0, -5.0, 70.4, 40.0, 5.0), direction_offset=0.0, out=None, keys=None, key_count=None,
-            records=None, num_tasks=1):
+            records=None, num_tasks=1, nms_type="rotate_nms", di=None):
     """head (B,22,P) planar float32; anchors (A,7) or (B,A,7); frustum (B,1,6,4,3) float64 or None.
     Returns dict(box (B,post,7), score (B,post), label (B,post) int32, count (B,) int32), all on the device.
     keys / key_count: the score-filter keys already produced by ssfa_fuse_head(keys=...) (sessd_predict_fused skips its own
@@ -2232,11 +2279,24 @@ def predict(head, anchors, frustum=None, score_thresh=0.3, pre_max=1000, post_ma
     frames' detection records to that ring.
     num_tasks = T > 1 (sessd_predict_tasks): head (B,T*22,P) = (B,T,22,P); anchors (T,A,7) shared by the frames or (B,T,A,7);
     every task runs its own score filter, top-k, NMS and post_max. Returns box (B,T*post,7), score / label (B,T*post), count (B,)
-    -- task 0's detections in NMS order, then task 1's, ...; label = task index -- and task_count (B,T); records (F,T*post,9)."""
+    -- task 0's detections in NMS order, then task 1's, ...; label = task index -- and task_count (B,T); records (F,T*post,9).
+    nms_type = "rotate_weighted_nms" (sessd_predict_di, any T): DI-NMS instead of the greedy rotated NMS, per (frame, task), with
+    the settings `di` (keys of DI_DEFAULTS; None = the reference's literals); pre_max <= 1024; nms_thresh is not read (as in the
+    reference). The selection stops at post_max kept boxes: the result also carries di_truncated (B,T) int32, 1 where candidates
+    were left, and di_keep (B,T,post) / di_keep_count (B,T): the kept candidates' ranks in the top-k order before the filters.
+    Returns the layout of num_tasks = T (task_count included) for every T."""
+    if nms_type not in NMS_TYPES:
+        raise ValueError("nms_type must be one of %s, got %r" % (NMS_TYPES, nms_type))
+    di_cfg = check_di({} if di is None else di, pre_max) if nms_type == "rotate_weighted_nms" else None
     _req(head, torch.float32, "head")
     _req(anchors, torch.float32, "anchors")
     B, ch, P = head.shape
     T = check_num_tasks(num_tasks)
+    if di_cfg is not None:
+        if T == 1 and anchors.dim() in (2, 3):  # (A,7) / (B,A,7) -> (1,A,7) / (B,1,A,7)
+            anchors = anchors.unsqueeze(-3)
+        return _predict_tasks(head, anchors, frustum, score_thresh, pre_max, post_max, nms_thresh, post_center_range,
+                              direction_offset, out, keys, key_count, records, T, di_cfg)
     if T > 1:
         return _predict_tasks(head, anchors, frustum, score_thresh, pre_max, post_max, nms_thresh, post_center_range,
                               direction_offset, out, keys, key_count, records, T)
@@ -2269,7 +2329,7 @@ def predict(head, anchors, frustum=None, score_thresh=0.3, pre_max=1000, post_ma
 
 
 def _predict_tasks(head, anchors, frustum, score_thresh, pre_max, post_max, nms_thresh, post_center_range, direction_offset, out,
-                   keys, key_count, records, T):
+                   keys, key_count, records, T, di_cfg=None):
     B, ch, P = head.shape
     if ch != T * TASK_HEAD_CH:
         raise ValueError("multi-task predict takes 22 planar head channels per task (one class, two rotations per location): "
@@ -2292,11 +2352,28 @@ def _predict_tasks(head, anchors, frustum, score_thresh, pre_max, post_max, nms_
     assert out["box"].numel() >= B * T * post_max * 7 and out["score"].numel() >= B * T * post_max
     if keys is not None:
         assert key_count is not None and keys.numel() >= B * T * 2 * P and key_count.numel() >= B * T
-    ws = workspace(lib.sessd_predict_tasks_workspace_bytes(B, T, 2 * P, pre_max, post_max), dev, "predict")
     rng = torch.tensor(post_center_range, dtype=torch.float32)
     rec, rcnt, rcur = records if records is not None else (None, None, None)
     if rec is not None:
         assert rec.shape[1] == T * post_max and rec.shape[2] == 9, "records: (frames, num_tasks * post_max, 9)"
+    if di_cfg is not None:
+        import ctypes
+        if "di_truncated" not in out:
+            out["di_truncated"] = torch.empty((B, T), dtype=torch.int32, device=dev)
+        assert out["di_truncated"].numel() >= B * T and out["di_truncated"].dtype == torch.int32
+        if "di_keep" not in out:  # the kept candidates' ranks before the filters (the reference's `selected`) and their number
+            out["di_keep"] = torch.empty((B, T, post_max), dtype=torch.int32, device=dev)
+            out["di_keep_count"] = torch.empty((B, T), dtype=torch.int32, device=dev)
+        ws = workspace(lib.sessd_predict_di_workspace_bytes(B, T, 2 * P, pre_max, post_max), dev, "predict")
+        check(lib.sessd_predict_di(head.data_ptr(), B, T, P, anchors.data_ptr(), per_frame, _p(frustum), float(score_thresh),
+                                   pre_max, post_max, float(nms_thresh), rng.data_ptr(), float(direction_offset),
+                                   out["box"].data_ptr(), out["score"].data_ptr(), out["label"].data_ptr(),
+                                   out["count"].data_ptr(), _p(out.get("task_count")), _p(keys), _p(key_count), _p(rec), _p(rcnt),
+                                   int(rec.shape[0]) if rec is not None else 0, _p(rcur), ctypes.addressof(di_cfg),
+                                   out["di_truncated"].data_ptr(), _p(out.get("di_truncated_sticky")), out["di_keep"].data_ptr(),
+                                   out["di_keep_count"].data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "predict_di")
+        return out
+    ws = workspace(lib.sessd_predict_tasks_workspace_bytes(B, T, 2 * P, pre_max, post_max), dev, "predict")
     check(lib.sessd_predict_tasks(head.data_ptr(), B, T, P, anchors.data_ptr(), per_frame, _p(frustum), float(score_thresh),
                                   pre_max, post_max, float(nms_thresh), rng.data_ptr(), float(direction_offset),
                                   out["box"].data_ptr(), out["score"].data_ptr(), out["label"].data_ptr(),

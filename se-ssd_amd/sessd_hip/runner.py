@@ -111,6 +111,7 @@ class HostFedPipeline:
         self._next_out = 0
         self._base = 0      # frames submitted before the last restart (submit() returns job-global indices)
         self._idle = True   # nothing in flight: the next submit() checks the device cursors against the host's ring state
+        self.nms_truncated = False   # set by finish(): the engines' sticky DI-NMS capacity flag
 
     def reset(self):
         """Start a new job: zero the device cursors and the sticky overflow flags (the engines must be idle). MANDATORY after
@@ -119,6 +120,7 @@ class HostFedPipeline:
         for e, st in zip(self.engines, self._st):
             e.record_cursor.zero_()
             e.err.zero_()
+            e.nms_truncated.zero_()
             st.update(submitted=0, fetched=0, pending=[], h2d=[None] * self.ring, consumed=[None] * self.ring)
         self._n, self._out, self._next_out = 0, {}, 0
         self._idle, self._base = False, 0
@@ -258,5 +260,8 @@ class HostFedPipeline:
             if int(e.err.item()) != 0:  # (every fetch carries the flag; this is the belt to those braces)
                 e.err.zero_()
                 raise RuntimeError("sparse level capacity overflow: raise `growth` or max_voxels")
+        # DI-NMS engines (test_cfg nms_type "rotate_weighted_nms"): did any frame of the job stop its selection at post_max with
+        # candidates left? Reported, never raised (the detections are the reference's keep list cut at post_max)
+        self.nms_truncated = any(int(e.nms_truncated.item()) != 0 for e in self.engines)
         self._idle = True
         return self._drain()

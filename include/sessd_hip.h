@@ -668,6 +668,18 @@ int sessd_ssfa_fuse_head_tasks(const float* x0, const float* x1, const float* w0
                                float* out, const float* head_w, const float* head_b, int num_tasks, float* head_out,
                                float score_thresh, unsigned long long* keys, int key_cap, int32_t* key_count,
                                sessd_stream_t stream);
+/* The counterpart for the SECOND-style RPN neck of the three-class config (rpn_v1.py:23-116 with one block and one stride-1
+ * up-sampler), which ends in ONE map: the up-sampler ConvTranspose2d(128, 128, 1, stride=1) + BatchNorm2d + ReLU
+ * (rpn_v1.py:60-71) on the f32 matrix cores, its result kept in LDS, and the heads of num_tasks tasks on it in the same launch.
+ * x (B, 128, num_pixels) = the last 3x3 layer's output; up_w (128, 128) = the transposed conv's weight as stored, [cin][cout]
+ * (u = relu(up_scale * (up_w^T x) + up_shift)); up_scale / up_shift (128) = the folded BatchNorm. head_w / head_b / head_out /
+ * keys / key_cap / key_count exactly as sessd_ssfa_fuse_head_tasks (same planar layout, same key encoding, counts zeroed by the
+ * caller; keys == NULL: no score filter). out (B, 128, num_pixels) receives the neck's output when not NULL. channels == 128 and
+ * 1 <= num_tasks <= 4, x / up_w / up_scale / up_shift / head_w / head_out not NULL: otherwise SESSD_EINVAL. */
+int sessd_rpn_up_head_tasks(const float* x, const float* up_w, const float* up_scale, const float* up_shift, int batch,
+                            int channels, int num_pixels, float* out, const float* head_w, const float* head_b, int num_tasks,
+                            float* head_out, float score_thresh, unsigned long long* keys, int key_cap, int32_t* key_count,
+                            sessd_stream_t stream);
 
 /* ------------------------------------------------------------------ predict / post-processing (a11-a14)
  * replaces det3d/models/bbox_heads/mg_head_sessd.py:893-1057 (MultiGroupHead.predict / get_task_detections),

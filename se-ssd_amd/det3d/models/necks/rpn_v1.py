@@ -22,14 +22,17 @@ class _Lowered:
     def __deepcopy__(self, memo):  # packed launches hold raw device pointers: a copied model re-packs on first use
         return _Lowered()
 
-    def get(self, name, conv, bn, deconv=False):
+    def get(self, name, conv, bn, deconv=False, transposed_1x1=False):
         # every tensor that feeds the packing / BN folding, plus the raw-pointer write counter (ops.param_generation)
         tensors = [conv.weight, conv.bias] + ([] if bn is None else [bn.weight, bn.bias, bn.running_mean, bn.running_var])
         key = (conv.weight.data_ptr(), ops.param_generation()) + tuple(-1 if t is None else t._version for t in tensors)
         hit = self._cache.get(name)
         if hit is None or hit[0] != key:
             w = conv.weight.detach()
-            pc = ops.pack_deconv2d_s2(w) if deconv else ops.pack_conv2d(w, conv.stride[0])
+            if transposed_1x1:  # ConvTranspose2d(cin, cout, 1, stride=1): y[o] = sum_i x[i] W[i][o], a 1x1 conv with W transposed
+                pc = ops.pack_conv2d(w.transpose(0, 1).contiguous(), 1)
+            else:
+                pc = ops.pack_deconv2d_s2(w) if deconv else ops.pack_conv2d(w, conv.stride[0])
             if bn is not None:
                 s, t = fold_bn(bn)
             else:
@@ -52,7 +55,9 @@ def _run_block(low, name, seq, x, residual=None):
             bn = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d) else None
             j = i + (2 if bn is not None else 1)
             relu = j < len(mods) and isinstance(mods[j], nn.ReLU)
-            pc, s, t = low.get("%s.%d" % (name, i), m, bn, isinstance(m, nn.ConvTranspose2d))
+            tr = isinstance(m, nn.ConvTranspose2d)
+            t1 = tr and tuple(m.kernel_size) == (1, 1) and tuple(m.stride) == (1, 1)
+            pc, s, t = low.get("%s.%d" % (name, i), m, bn, tr and not t1, transposed_1x1=t1)
             last = (j + (1 if relu else 0)) >= len(mods)
             x = ops.conv2d(x, pc, s, t, relu, residual if last else None)
             i = j + (1 if relu else 0)
@@ -166,7 +171,10 @@ class SSFA(nn.Module):
 @NECKS.register_module
 class RPN(nn.Module):
     """SECOND-style RPN (rpn_v1.py:23-116): blocks of [pad, conv s, bn, relu, (conv, bn, relu)*n] + deconv/conv upsamplers,
-    outputs concatenated. Only stride-1/2 3x3 convs and 1x1 / stride-2 3x3 transposed convs are lowered."""
+    outputs concatenated. The up-sampler of an integer stride s >= 1 is ConvTranspose2d(cin, cout, s, stride=s) as in the reference
+    (s = 1, the three-class config: a 1x1 conv with the weight transposed, lowered through the 1x1 kernels); a stride below 1 is a
+    strided Conv2d (not in the reference at this commit). Lowered: stride-1/2 3x3 convs, 1x1 convs, the k = 1 stride-1 transposed
+    conv; a transposed up-sampler of stride >= 2 runs in plain torch."""
 
     def __init__(self, layer_nums, ds_layer_strides, ds_num_filters, us_layer_strides, us_num_filters,
                  num_input_features, norm_cfg=None, name="rpn", logger=None, **kwargs):
@@ -193,8 +201,10 @@ class RPN(nn.Module):
             if i - self._upsample_start_idx >= 0:
                 k = i - self._upsample_start_idx
                 stride = us_layer_strides[k]
-                if stride > 1:
-                    up = nn.ConvTranspose2d(ds_num_filters[i], us_num_filters[k], stride, stride=stride, bias=False)
+                if stride >= 1:
+                    if int(stride) != stride:
+                        raise ValueError("RPN: an up-sampling stride >= 1 must be an integer, got %r" % (stride,))
+                    up = nn.ConvTranspose2d(ds_num_filters[i], us_num_filters[k], int(stride), stride=int(stride), bias=False)
                 else:
                     up = nn.Conv2d(ds_num_filters[i], us_num_filters[k], int(np.round(1 / stride)), stride=int(np.round(1 / stride)), bias=False)
                 deblocks.append(Sequential(up, build_norm_layer(norm_cfg, us_num_filters[k])[1], nn.ReLU()))
@@ -210,8 +220,8 @@ class RPN(nn.Module):
             x = _run_block(self._low, "blk%d" % i, self.blocks[i], x)
             if i - self._upsample_start_idx >= 0:
                 de = self.deblocks[i - self._upsample_start_idx]
-                if isinstance(de[0], nn.ConvTranspose2d):
-                    ups.append(de(x))  # k == stride transposed conv: plain torch (not on the SE-SSD path)
+                if isinstance(de[0], nn.ConvTranspose2d) and tuple(de[0].stride) != (1, 1):
+                    ups.append(de(x))  # k == stride >= 2 transposed conv: plain torch (not on the SE-SSD path)
                 else:
                     ups.append(_run_block(self._low, "de%d" % i, de, x))
         return torch.cat(ups, dim=1) if len(ups) > 0 else x

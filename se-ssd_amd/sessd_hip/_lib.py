@@ -124,6 +124,7 @@ SIGNATURES = {
     "sessd_predict_fused": (i32, [vp, i32, i32, vp, i32, vp, f32, i32, i32, f32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, sz, vp]),
     "sessd_ssfa_fuse_head_keys": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, i32, vp, vp]),
     "sessd_ssfa_fuse_head_tasks": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, i32, vp, vp]),
+    "sessd_rpn_up_head_tasks": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, i32, vp, vp]),
     "sessd_predict_tasks_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "sessd_predict_tasks": (i32, [vp, i32, i32, i32, vp, i32, vp, f32, i32, i32, f32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp,
                                   sz, vp]),

@@ -20,6 +20,18 @@ def kitti_3class_model():
     return kitti_car_model(tasks=KITTI_3CLASS_TASKS)
 
 
+def kitti_3class_rpn_model():
+    """The model dict of the reference's three-class config (examples/second/configs/
+    kitti_all_vfev3_spmiddlefhd_rpn1_mghead_syncbn.py:62-115): the three one-class tasks on the SECOND-style RPN neck (one block
+    of 1 + 5 3x3 layers, one stride-1 up-sampler) instead of SSFA. Anchors: kitti_3class_anchors(). Inference only."""
+    m = kitti_car_model(tasks=KITTI_3CLASS_TASKS)
+    m["neck"] = dict(type="RPN", layer_nums=[5], ds_layer_strides=[1], ds_num_filters=[128], us_layer_strides=[1],
+                     us_num_filters=[128], num_input_features=128, norm_cfg=None, logger=logging.getLogger("RPN"))
+    m["bbox_head"]["in_channels"] = sum([128])
+    m["bbox_head"]["weights"] = [1]
+    return m
+
+
 def kitti_3class_anchors(feature_hw=(200, 176), voxel_range=None):
     """(3, H*W*2, 7) anchors of KITTI_3CLASS_ANCHORS over the x / y extent of `voxel_range` (default: the KITTI range)."""
     from .anchors import create_task_anchors
@@ -65,7 +77,7 @@ def build_synthetic_detector(device, seed=0, calib_frame_seed=0, max_voxels=1600
     """det3d-mirror VoxelNet with seeded weights, BatchNorm statistics calibrated on one synthetic frame (on `device`) of the
     workload's own density (supersample = 3 for the 200 k-point dense scenes): random weights calibrated on a sparse scan give
     activations (and decoded boxes) of absurd magnitude on a dense one.
-    model_cfg: another model dict (kitti_3class_model()); voxel_range: a reduced range (the frame is cropped by the voxelizer)."""
+    model_cfg: another model dict (kitti_3class_model(), kitti_3class_rpn_model()); voxel_range: a reduced range (the frame is cropped by the voxelizer)."""
     import torch
     from det3d.models import build_detector
     from . import ops, synth

@@ -1,4 +1,5 @@
-"""Whole-frame inference engine: voxelize -> SpMiddleFHD -> SSFA -> heads -> predict on one HIP stream.
+"""Whole-frame inference engine: voxelize -> SpMiddleFHD -> SSFA (or the SECOND-style RPN neck of the three-class config) -> heads
+-> predict on one HIP stream.
 
 All device buffers are allocated once for fixed capacities, every data-dependent count stays on the
 device, and nothing in `enqueue()` synchronises or allocates -- so a frame is ~60 back-to-back kernel
@@ -173,6 +174,89 @@ class DensePlan:
         self.head_b = hb
 
 
+def _const_step(conv, bn, c):
+    """relu(scale * (sum_k W[co][ci][k]) @ c + shift): what a conv + BN + ReLU layer computes on the constant map c, float64"""
+    s_, t_ = fold_bn(bn)
+    return torch.relu(s_.double().cpu() * (conv.weight.detach().double().cpu().sum((2, 3)) @ c) + t_.double().cpu())
+
+
+def rpn_tile_constants(neck):
+    """The `step` recurrence of active_tile_constants over the 3x3 stride-1 layers of the RPN neck's one block (rpn_v1.py:84-99),
+    starting from 0 (the BEV map away from the sparse sites): entry l = what layer l computes where its input is constant, away
+    from the border. tests/test_rpn_mirror_cpu.py holds them to the modules applied to constant maps."""
+    blk = neck.blocks[0]
+    c = torch.zeros(blk[1].weight.shape[1], dtype=torch.float64)
+    chain = []
+    for ci in range(1, len(blk), 3):
+        c = _const_step(blk[ci], blk[ci + 1], c)
+        chain.append(c)
+    return chain
+
+
+def check_rpn_neck(neck):
+    """The RPN necks the engine lowers, as ValueErrors that name the limit (nothing here touches the device): what the three-class
+    config uses -- ONE block of ZeroPad2d(1) + unpadded 3x3 conv, then layer_nums[0] padded 3x3 convs, all stride 1, 128 -> 128,
+    each + BatchNorm2d + ReLU, and ONE stride-1 up-sampler ConvTranspose2d(128, 128, 1, stride=1) + BatchNorm2d + ReLU."""
+    import torch.nn as nn
+    if len(neck.blocks) != 1 or len(neck.deblocks) != 1:
+        raise ValueError("the engine lowers an RPN neck of ONE block with ONE up-sampler (layer_nums=[n], us_layer_strides=[1]); "
+                         "this one has %d blocks and %d up-samplers (multi-block SECOND necks are not supported)"
+                         % (len(neck.blocks), len(neck.deblocks)))
+    blk, de = list(neck.blocks[0]._modules.values()), list(neck.deblocks[0]._modules.values())
+    convs = [m for m in blk if isinstance(m, nn.Conv2d)]
+    for m in convs:
+        if tuple(m.stride) != (1, 1) or tuple(m.kernel_size) != (3, 3):
+            raise ValueError("the engine lowers an RPN block of 3x3 stride-1 convs (ds_layer_strides=[1]); this one has kernel %s "
+                             "stride %s" % (tuple(m.kernel_size), tuple(m.stride)))
+        if m.in_channels != 128 or m.out_channels != 128:
+            raise ValueError("the engine lowers an RPN block of 128 filters on a 128-channel BEV map (ds_num_filters=[128], "
+                             "num_input_features=128); this one has a %d -> %d conv" % (m.in_channels, m.out_channels))
+    ok = len(blk) == 1 + 3 * len(convs) and isinstance(blk[0], nn.ZeroPad2d) and tuple(blk[0].padding) == (1, 1, 1, 1)
+    for i, m in enumerate(convs):
+        ok = ok and blk[1 + 3 * i] is m and isinstance(blk[2 + 3 * i], nn.BatchNorm2d) and isinstance(blk[3 + 3 * i], nn.ReLU)
+        ok = ok and tuple(m.padding) == ((0, 0) if i == 0 else (1, 1)) and m.bias is None
+    if not ok or not convs:
+        raise ValueError("the engine lowers an RPN block of the form ZeroPad2d(1), (Conv2d 3x3, BatchNorm2d, ReLU) x (1 + n)")
+    up = de[0]
+    if not (len(de) == 3 and isinstance(up, nn.ConvTranspose2d) and tuple(up.kernel_size) == (1, 1) and tuple(up.stride) == (1, 1)
+            and isinstance(de[1], nn.BatchNorm2d) and isinstance(de[2], nn.ReLU) and up.bias is None):
+        raise ValueError("the engine lowers an RPN up-sampler of stride 1: ConvTranspose2d(128, 128, 1, stride=1) + BatchNorm2d + "
+                         "ReLU (us_layer_strides=[1]); this one is %r" % (up,))
+    if up.in_channels != 128 or up.out_channels != 128:
+        raise ValueError("the engine lowers an RPN up-sampler of 128 -> 128 channels (us_num_filters=[128]); this one is %d -> %d"
+                         % (up.in_channels, up.out_channels))
+
+
+class RpnPlan:
+    """The RPN neck of the three-class config + heads lowered to launches (det3d/models/necks/rpn_v1.py:23-116 with
+    layer_nums=[n], strides 1, 128 filters; mg_head_sessd.py:202-230): `layers` = the 1 + n 3x3 stride-1 layers (index 0 is
+    ZeroPad2d(1) + unpadded conv == pad 1), `up` = the stride-1 up-sampler as a 1x1 conv with the weight transposed (the
+    two-launch form), `up_w` = its weight as stored, [cin][cout] (the fused tail + heads launch)."""
+    form = "rpn"
+
+    def __init__(self, neck, head_tasks, device):
+        check_rpn_neck(neck)
+        blk, de = neck.blocks[0], neck.deblocks[0]
+
+        def cbr(conv, bn, w=None):
+            s, t = fold_bn(bn)
+            return ops.pack_conv2d((conv.weight.detach() if w is None else w).to(device), 1), s.to(device), t.to(device)
+
+        self.layers = [cbr(blk[ci], blk[ci + 1]) for ci in range(1, len(blk), 3)]
+        self.act_const = [v.float().to(device).contiguous() for v in rpn_tile_constants(neck)]
+        wt = de[0].weight.detach().float()   # (cin, cout, 1, 1): y[o] = sum_i x[i] * W[i][o]
+        self.up = cbr(de[0], de[1], w=wt.transpose(0, 1).contiguous())
+        self.up_w = wt.reshape(wt.shape[0], wt.shape[1]).to(device).contiguous()
+        hw, hb = pack_task_heads(head_tasks)
+        if hw.shape[1] != 128:
+            raise ValueError("the heads behind an RPN neck read its 128 channels (in_channels=128), got %d" % hw.shape[1])
+        hw, hb = hw.detach().to(device), hb.detach().to(device).float().contiguous()
+        self.num_tasks = hw.shape[0] // ops.TASK_HEAD_CH
+        self.head = (ops.pack_conv2d(hw), None, hb)
+        self.head_w = hw.reshape(hw.shape[0], -1).float().contiguous()  # row-major (T * 22, C): the fused tail + heads launch
+        self.head_b = hb
+
+
 class InferenceEngine:
     def __init__(self, model, voxel_range, voxel_size, max_points_per_voxel, max_voxels, test_cfg, batch_size=1,
                  max_points_per_frame=32768, device=None, growth=(1.5, 1.0, 0.75, 0.75), anchors=None,
@@ -187,6 +271,11 @@ class InferenceEngine:
         nms = test_cfg["nms"] if isinstance(test_cfg, dict) else test_cfg.nms
         self.nms_type, self.di = ops.nms_settings(nms, int(nms["nms_pre_max_size"]))
         self.di_cfg = ops.check_di(self.di) if self.di is not None else None
+        # the neck's form: "ssfa" (DensePlan) or "rpn" (RpnPlan: the SECOND-style neck of the three-class config, whose limits are
+        # checked here, too)
+        self.form = "rpn" if type(model.neck).__name__ == "RPN" else "ssfa"
+        if self.form == "rpn":
+            check_rpn_neck(model.neck)
         self.dev = torch.device("cuda:0") if device is None else device
         dev = self.dev
         self.B = int(batch_size)
@@ -201,7 +290,7 @@ class InferenceEngine:
         convs = [m for m in model.backbone.middle_conv if hasattr(m, "indice_key")]
         bns = [m for m in model.backbone.middle_conv if isinstance(m, torch.nn.BatchNorm1d)]
         self.sp = SparsePlan(convs, bns, SPMIDDLE_LAYERS, dev)
-        self.dn = DensePlan(model.neck, model.bbox_head.tasks, dev)
+        self.dn = (RpnPlan if self.form == "rpn" else DensePlan)(model.neck, model.bbox_head.tasks, dev)
         T = self.num_tasks = self.dn.num_tasks  # (frame, task) goes through predict as the virtual frame b * T + t
         nms = test_cfg["nms"] if isinstance(test_cfg, dict) else test_cfg.nms
         self.score_thresh = float(test_cfg["score_threshold"])
@@ -306,13 +395,25 @@ class InferenceEngine:
             else:
                 L["indices"], L["n"] = self.chain.indices[li - 1], self.chain.n_dev[li - 1]
         self.bev = torch.zeros((B, self.bev_c, H, W), dtype=f32, device=dev)
-        self.t = {k: E(B, 128, H, W) for k in ("a", "b", "x0", "tr0", "out")}
+        # an RPN engine: one buffer per layer of the block ("l0" ... : a layer in active-tile mode writes its listed tiles only, the
+        # rest of ITS map holds its constant from the head of the stage; without a tile-activity program the layers ping-pong
+        # between "l0" and "l1"), "out" = the up-sampler's output (the two-launch form, or keep_ssfa); no branches, no
+        # half-resolution maps
+        tiles_ok = bool(active_tiles) and H <= 256 and W <= 192 and H % 4 == 0 and W % 8 == 0
+        if self.form == "rpn":
+            nl = len(self.dn.layers)
+            if nl > 8:
+                tiles_ok = False   # sessd_bev_tile_activity takes at most eight slots
+            self.t = {k: E(B, 128, H, W) for k in ["l%d" % i for i in range(nl if tiles_ok else min(nl, 2))] + ["out"]}
+        else:
+            self.t = {k: E(B, 128, H, W) for k in ("a", "b", "x0", "tr0", "out")}
         # the two branches after the transposed convs are one shape: adjacent buffers, so that conv_0 / conv_1 can be one launch
-        self.t["mid"], self.t["o"] = E(2 * B, 128, H, W), E(2 * B, 128, H, W)
-        for k, src in (("mid0", "mid"), ("mid1", "mid"), ("o0", "o"), ("o1", "o")):
-            self.t[k] = self.t[src][:B] if k.endswith("0") else self.t[src][B:]
+        if self.form == "ssfa":
+            self.t["mid"], self.t["o"] = E(2 * B, 128, H, W), E(2 * B, 128, H, W)
+            for k, src in (("mid0", "mid"), ("mid1", "mid"), ("o0", "o"), ("o1", "o")):
+                self.t[k] = self.t[src][:B] if k.endswith("0") else self.t[src][B:]
         self.merge_branch_convs = True  # conv_0 + conv_1 as one stream-K Winograd launch when both were tuned to the same shape
-        self.h = {k: E(B, 256, H // 2, W // 2) for k in ("a", "b", "x1", "tr1")}
+        self.h = {k: E(B, 256, H // 2, W // 2) for k in ("a", "b", "x1", "tr1")} if self.form == "ssfa" else {}
         self.head = E(B, T * 22, H * W)
         if anchors is None:
             if T > 1:
@@ -363,9 +464,19 @@ class InferenceEngine:
         # convs as one launch over 2x2 tiles of their input (direct kernel, (tile_cfg, 0); buffers: trans_1 in, mid0 / mid1 out).
         self.active_tiles = bool(active_tiles)
         self.active_cfg = {}   # id -> (stream-K shape, min_rounds) / (30, min_rounds), chosen by autotune(); empty = dense launches
-        ok = self.active_tiles and H <= 256 and W <= 192 and H % 4 == 0 and W % 8 == 0
-        self.ta = ops.TileActivity(B, H, W, [0, 0, 0, 2, 0, 0, 3, 4, 0], dev) if ok else None
-        self.ACTIVE_SLOTS = {0: ("b0.0", self.dn.b0[0], self.bev, self.t["a"]), 1: ("b0.1", self.dn.b0[1], self.t["a"], self.t["b"]),
+        # The per-form tables below are instance data chosen by the plan's form. An RPN engine: the program of its stride-1 layers is
+        # {0, 0, 0, 0, 0, 0}, layer i = slot i, all on the Winograd list launches; outputs 0 .. n-2 have one reader each, the next
+        # layer on the same grid (near-fill kind 0), the last one is read by the tail launch over the whole map (filled everywhere).
+        ok = tiles_ok
+        if self.form == "rpn":
+            nl = len(self.dn.layers)
+            self.ta = ops.TileActivity(B, H, W, [0] * nl, dev) if ok else None
+            bufs = [self.bev] + [self.t["l%d" % (i if ok else i & 1)] for i in range(nl)]
+            self._rpn_bufs = bufs
+            self.ACTIVE_SLOTS_RPN = {i: ("blk0.%d" % i, self.dn.layers[i], bufs[i], bufs[i + 1]) for i in range(nl)} if ok else {}
+        else:
+            self.ta = ops.TileActivity(B, H, W, [0, 0, 0, 2, 0, 0, 3, 4, 0], dev) if ok else None
+        self.ACTIVE_SLOTS = self.ACTIVE_SLOTS_RPN if self.form == "rpn" else {0: ("b0.0", self.dn.b0[0], self.bev, self.t["a"]), 1: ("b0.1", self.dn.b0[1], self.t["a"], self.t["b"]),
                              2: ("b0.2", self.dn.b0[2], self.t["b"], self.t["x0"]), 3: ("b1.0", self.dn.b1[0], self.t["x0"], self.h["a"]),
                              4: ("b1.1", self.dn.b1[1], self.h["a"], self.h["b"]), 5: ("b1.2", self.dn.b1[2], self.h["b"], self.h["x1"]),
                              6: ("trans_0", self.dn.trans_0, self.t["x0"], self.t["tr0"]),
@@ -375,10 +486,23 @@ class InferenceEngine:
         self.ACTIVE_MASK = {0: 0, 1: 1, 2: 2, 3: 3, 4: 4, 5: 5, 6: 2, 7: 5, 8: 6, 9: 7}
         self.ACTIVE_SK = (3, 6, 7)
         self.ACTIVE_PAIR = 8
+        self.NEAR_READER = type(self).NEAR_READER
+        self.DEFAULT_ACTIVE_CFG = type(self).DEFAULT_ACTIVE_CFG
         # Id 9 (round 6) = conv_0 and conv_1 (rpn_v1.py:200-210) over the 2x2 tiles of the transposed convs' OUTPUT that can differ from
         # their per-parity-class constants (step program {.., 3, 4, 0}: 0.69 - 0.85 of the tiles of a 20 k-point scan): two Winograd list
         # launches (one per branch, one list), the rest of o0 / o1 filled with the (4, cout) parity constants
         self.ACTIVE_CONV = 9
+        if self.form == "rpn":
+            nl = len(self.dn.layers)
+            self.ACTIVE_MASK = {i: i for i in self.ACTIVE_SLOTS}
+            self.ACTIVE_SK, self.ACTIVE_PAIR, self.ACTIVE_CONV = (), -1, -1   # no stride-2 / 1x1 list layers, no pair, no branches
+            self.NEAR_READER = {i: i + 1 for i in range(nl - 1)}
+            # defaults = what autotune() chose on MI355X for the full-size three-class engine (DESIGN.md section 3,
+            # profiles/rpn_tail_and_lists.json): the four-wave shape, stream-K shares of >= 4 rounds for the first (shortest) list
+            # and whole units for the next three; the eight-wave shape (bf16 split where built) on whole units for the last two
+            s8 = 3 if WINO_SPLIT else 0
+            tuned = [(1, 4), (1, -1), (1, -1), (1, -1), (s8, -1), (s8, -1)]
+            self.DEFAULT_ACTIVE_CFG = {i: tuned[min(i, 5)] for i in self.ACTIVE_SLOTS}
         self.allow_active_conv = True   # autotune() may put conv_0 / conv_1 on their tile list (bench.py --no-active-conv: A/B)
         self.near_fill = True   # fill only the tiles a list-driven reader can reach where that reader is the map's only one
         self.coarse_fill = True  # ... also where the readers run on a grid twice as coarse (x0, tr0) or on the map's own list (x1): round 5
@@ -403,8 +527,14 @@ class InferenceEngine:
         self._marks = None
         self.tile_cfg = {}
         self.sk_ws = None  # workspace of the stream-K launches, tile_cfg 22 / 23 / 30 (autotune allocates it)
-        self.fuse_head = True   # SSFA fusion tail + the 1x1 heads in one launch (the SSFA output stays in registers)
-        self.keep_ssfa = False  # with fuse_head: also write the SSFA output to self.t["out"] (tests compare it with the oracle)
+        # SSFA fusion tail + the 1x1 heads in one launch (the SSFA output stays in registers); an RPN engine: the stride-1 up-sampler
+        # + the heads in one launch (ops.rpn_up_head, its output stays in LDS). False: the two-launch form through ops.conv2d and
+        # predict's own score filter
+        # MEASURED for the RPN form on the full-size three-class engine: the fused launch 61 us against
+        # 21.5 + 16.5 us for the two launches, 619 against 600 us per replayed frame -- so an RPN engine defaults to the two-launch
+        # form and the fused kernel stays selectable (fuse_head = True)
+        self.fuse_head = self.form != "rpn"
+        self.keep_ssfa = False  # with fuse_head: also write the neck's output to self.t["out"] (tests compare it with the oracle)
         self.allow_streamk = True  # autotune may choose the stream-K kernels (Winograd: tile_cfg 22 / 23; LDS-tiled direct: 30)
         self.allow_offset_split = True  # autotune may choose the offset-split sparse conv (see sessd_sparse_conv)
         self.sk_workgroups = 0  # persistent workgroups of those launches (0 = one or two per CU; fewer leaves CUs to a second stream)
@@ -518,6 +648,8 @@ class InferenceEngine:
                 rd = self.NEAR_READER.get(l)
                 if rd is not None and rd in ids and rd not in self.ACTIVE_SK:
                     nr = self.ACTIVE_MASK[rd]
+                elif self.form != "ssfa":
+                    pass
                 elif self.coarse_fill and l == 2 and 3 in ids and 6 in ids:
                     nr, kind = self.ACTIVE_MASK[3], 2
                 elif self.coarse_fill and l == 6 and self.ACTIVE_PAIR in ids:
@@ -590,9 +722,25 @@ class InferenceEngine:
         """The configuration autotune() ends in on MI355X, WITHOUT timing anything: the neck's 3x3 stride-1 layers on the stream-K
         Winograd kernels, the stride-2 / 1x1 layers on the LDS-tiled stream-K kernel, and every layer of ACTIVE_SLOTS over its
         tile list with the given (kernel, minimum share) choices (default: all ten). Allocates the stream-K workspace. Used by
-        __graft_entry__.smoke() and the tests, so that what the driver smokes is the kind of configuration bench.py times."""
+        __graft_entry__.smoke() and the tests, so that what the driver smokes is the kind of configuration bench.py times.
+        An RPN engine: its 3x3 layers over their lists with its own DEFAULT_ACTIVE_CFG (the choice measured on MI355X)."""
         if self.ta is None:
             raise RuntimeError("this engine has no tile-activity program (active_tiles=False or an unsupported BEV size)")
+        if self.form == "rpn":
+            # an RPN engine: its 3x3 layers on the stream-K Winograd kernel (8 waves x 128 couts, exact f32) where they run as
+            # full-map launches, and every layer over its tile list with the given (shape, minimum share) choices
+            self.tile_cfg.update({"blk0.%d" % i: 22 for i in range(len(self.dn.layers))})
+            need = max(int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(self.B, self.H, self.W, 128, sh, 0)) for sh in (0, 1))
+            if self.sk_ws is None or self.sk_ws.numel() < need:
+                self.sk_ws = torch.zeros(need, dtype=torch.uint8, device=self.dev)
+            cfg = dict(self.DEFAULT_ACTIVE_CFG if active_cfg is None else active_cfg)
+            for l, (shape, mr) in cfg.items():
+                if l not in self.ACTIVE_SLOTS:
+                    raise ValueError("an RPN engine's list layers are %s, got %r" % (sorted(self.ACTIVE_SLOTS), l))
+                if self.ACTIVE_SLOTS[l][1][0].upk_sk(shape) is None:
+                    raise ValueError("active-tile layer %s: no stream-K Winograd packing for shape %d" % (self.ACTIVE_SLOTS[l][0], shape))
+            self.active_cfg = cfg
+            return self.active_cfg
         self.tile_cfg.update({"b0.0": 22, "b0.1": 22, "b0.2": 23, "b1.0": 30, "b1.1": 23, "b1.2": 22, "trans_0": 30, "trans_1": 30,
                               "conv_0": 22, "conv_1": 22})
         B = self.B
@@ -997,6 +1145,8 @@ class InferenceEngine:
                 self._kmarks.append(("tile_activity+fill", e0, e1))
         if part == "front":
             return self.out
+        if self.form == "rpn":
+            return self._enqueue_predict(s, self._enqueue_rpn_neck())
         x = self._conv(self.bev, d.b0[0], t["a"], name="b0.0", active=0 if 0 in act else None)
         x = self._conv(x, d.b0[1], t["b"], name="b0.1", active=1 if 1 in act else None)
         x0 = self._conv(x, d.b0[2], t["x0"], name="b0.2", active=2 if 2 in act else None)
@@ -1081,6 +1231,37 @@ class InferenceEngine:
             ops.ssfa_fuse(o0, o1, d.w0, d.w1, *d.wbn, out=t["out"])
             self._conv(t["out"], d.head, self.head.view(B, self.num_tasks * 22, self.H, self.W), relu=False, name="head")
         self._mark("ssfa_head")
+        return self._enqueue_predict(s, fused_keys)
+
+    def _enqueue_rpn_neck(self):
+        """The RPN neck (rpn_v1.py:107-116) + heads: the block's 3x3 layers, then the up-sampler + the heads of every task (+ the
+        score-filter keys) in one launch, or as two ops.conv2d launches. Returns whether the launch wrote the keys."""
+        d, t, B = self.dn, self.t, self.B
+        act = self._active_layers()
+        x = self.bev
+        for i, layer in enumerate(d.layers):
+            x = self._conv(x, layer, self._rpn_bufs[i + 1], name="blk0.%d" % i, active=i if i in act else None)
+        fused_keys = False
+        if self.fuse_head and self._tuning is None:
+            if self._kmarks is not None:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+            fused_keys = True
+            ops.rpn_up_head(x, d.up_w, d.up[1], d.up[2], d.head_w, d.head_b, head_out=self.head,
+                            out=t["out"] if self.keep_ssfa else None, score_thresh=self.score_thresh,
+                            keys=self.keys if self.fuse_predict else None, key_count=self.key_count if self.fuse_predict else None,
+                            num_tasks=self.num_tasks)
+            if self._kmarks is not None:
+                e1.record()
+                self._kmarks.append(("rpn_tail+head", e0, e1))
+        else:
+            self._conv(x, d.up, t["out"], name="up")
+            self._conv(t["out"], d.head, self.head.view(B, self.num_tasks * 22, self.H, self.W), relu=False, name="head")
+        self._mark("ssfa_head")
+        return fused_keys
+
+    def _enqueue_predict(self, s, fused_keys):
+        B = self.B
         # ---- predict (a11-a14): top-k + decode, suppression mask, greedy walk + filters (+ the frame's record): 3 launches
         use_keys = fused_keys and self.fuse_predict
         rec = self.records is not None

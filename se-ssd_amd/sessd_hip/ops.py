@@ -2210,6 +2210,37 @@ def ssfa_fuse_head(x0, x1, w0, w1, s0, t0, s1, t1, head_w, head_b, head_out=None
     return head_out
 
 
+def rpn_up_head(x, up_w, up_scale, up_shift, head_w, head_b, head_out=None, out=None, score_thresh=0.0, keys=None, key_count=None,
+                num_tasks=1):
+    """The tail of the three-class config's RPN neck + the 1x1 heads in one launch (sessd_rpn_up_head_tasks): x (B, 128, H, W) =
+    the last 3x3 layer's output; up_w (128, 128) [cin][cout] = the ConvTranspose2d(128, 128, 1, stride=1) weight as stored,
+    up_scale / up_shift (128) its folded BatchNorm (ReLU follows): u = relu(up_scale * (up_w^T x) + up_shift) on the f32 matrix
+    cores, kept in LDS. head_w (T*22, 128), head_b (T*22) or None -> head_out (B, T*22, H*W) = (B, T, 22, H*W) planar; `out`
+    (B, 128, H, W): optional buffer that receives u. keys (B, T, 2*H*W) int64 + key_count (B*T,) int32 (zeroed by the caller):
+    predict's score-filter keys per (frame, task), as ssfa_fuse_head writes them."""
+    for t, name in ((x, "x"), (up_w, "up_w"), (up_scale, "up_scale"), (up_shift, "up_shift"), (head_w, "head_w")):
+        _req(t, torch.float32, name)
+    B, C, H, W = x.shape
+    nout = head_w.shape[0]
+    T = check_num_tasks(num_tasks)
+    if C != 128 or up_w.numel() != C * C or up_scale.numel() != C or up_shift.numel() != C or head_w.shape[1] != C:
+        raise ValueError("rpn_up_head takes 128 channels in and out (x (B, 128, H, W), up_w (128, 128), up_scale / up_shift (128), "
+                         "head_w (T*22, 128)): got %d channels, up_w %s" % (C, tuple(up_w.shape)))
+    if nout != T * TASK_HEAD_CH or (head_b is not None and head_b.numel() != nout):
+        raise ValueError("head weights must be (num_tasks * 22, C) with a (num_tasks * 22) bias: %d channels for %d tasks" % (nout, T))
+    if head_out is None:
+        head_out = torch.empty((B, nout, H * W), dtype=torch.float32, device=x.device)
+    if keys is not None:
+        assert key_count is not None and keys.dtype == torch.int64 and key_count.dtype == torch.int32 and keys.is_contiguous()
+        assert keys.numel() >= B * T * 2 * H * W and key_count.numel() >= B * T
+    assert head_out.numel() >= B * nout * H * W and head_out.is_contiguous()
+    assert out is None or (out.numel() >= B * C * H * W and out.is_contiguous())
+    check(lib.sessd_rpn_up_head_tasks(x.data_ptr(), up_w.data_ptr(), up_scale.data_ptr(), up_shift.data_ptr(), B, C, H * W, _p(out),
+                                      head_w.data_ptr(), _p(head_b), T, head_out.data_ptr(), float(score_thresh), _p(keys),
+                                      2 * H * W if keys is not None else 0, _p(key_count), _stream()), "rpn_up_head_tasks")
+    return head_out
+
+
 def fill_multi(segments):
     """[(tensor, 32-bit pattern), ...] (<= 4, 16-byte aligned, sizes multiples of 4 bytes) cleared in ONE launch."""
     import ctypes

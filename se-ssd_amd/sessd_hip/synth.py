@@ -218,14 +218,22 @@ def calibrate_synthetic_model(model, voxel_features, coors, batch_size, input_sh
             run = sparse_runner if sparse_runner is not None else model.backbone
             x = run(voxel_features, coors, batch_size, input_shape)
             nk = model.neck
-            x0 = nk.bottom_up_block_0(x)
-            x1 = nk.bottom_up_block_1(x0)
-            t0, t1 = nk.trans_0(x0), nk.trans_1(x1)
-            m0 = nk.deconv_block_0(t1) + t0
-            m1 = nk.deconv_block_1(t1)
-            o0, o1 = nk.conv_0(m0), nk.conv_1(m1)
-            w = torch.softmax(torch.cat([nk.w_0(o0), nk.w_1(o1)], 1), 1)
-            out = o0 * w[:, 0:1] + o1 * w[:, 1:]
+            if type(nk).__name__ == "RPN":  # SECOND-style neck (rpn_v1.py:107-116): the torch modules, block by block
+                ups = []
+                for i, blk in enumerate(nk.blocks):
+                    x = blk(x)
+                    if i - nk._upsample_start_idx >= 0:
+                        ups.append(nk.deblocks[i - nk._upsample_start_idx](x))
+                out = torch.cat(ups, 1) if ups else x
+            else:
+                x0 = nk.bottom_up_block_0(x)
+                x1 = nk.bottom_up_block_1(x0)
+                t0, t1 = nk.trans_0(x0), nk.trans_1(x1)
+                m0 = nk.deconv_block_0(t1) + t0
+                m1 = nk.deconv_block_1(t1)
+                o0, o1 = nk.conv_0(m0), nk.conv_1(m1)
+                w = torch.softmax(torch.cat([nk.w_0(o0), nk.w_1(o1)], 1), 1)
+                out = o0 * w[:, 0:1] + o1 * w[:, 1:]
             for head in model.bbox_head.tasks:  # every task of a multi-task head gets its own candidates
                 head.conv_cls.bias.zero_()
                 logits = F.conv2d(out, head.conv_cls.weight).reshape(-1)

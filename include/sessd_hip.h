@@ -82,6 +82,28 @@ int sessd_voxelize_frames(const float* points, int batch, int points_per_frame, 
 int sessd_stage_points(const float* points, int num_points, float* dst, int capacity, sessd_stream_t stream);
 int sessd_vfe_mean(const float* voxels, const int32_t* num_points, const int32_t* num_voxels_dev, int num_voxels_host,
                    int max_points_per_voxel, int ndim, int num_features, float* out, sessd_stream_t stream);
+/* PointPillars front end (csrc/pillar.hip): replaces det3d/models/readers/pillar_encoder.py:114-153 (PillarFeatureNet.forward
+ * with ONE PFNLayer, eval mode) and :173-208 (PointPillarsScatter.forward) in one launch, one wave per pillar.
+ * voxels (N_cap, T, 4) [x, y, z, r], num_points (N_cap), coors (N_cap, 4) [b, z, y, x]; live pillars = num_voxels_host, or
+ * *num_voxels_dev when not NULL (never more than num_voxels_host); rows beyond are neither read nor written.
+ * Per point the K = 9 (with_distance: 10) columns [x, y, z, r, x - mx, y - my, z - mz, fcx, fcy (, |xyz|)], m = sum of the
+ * pillar's points / num_points, fcx = -(float(x_coor) * vx + x_offset), fcy = -(float(y_coor) * vy + y_offset) -- per-pillar
+ * constants in this fork (:126-133), rounded as written (no contraction). feat[v][c] = max over the T slots of
+ * relu(scale[c] * (weight[c] . columns) + shift[c]); weight (channels, K) as nn.Linear stores it, scale / shift (channels) the
+ * folded BatchNorm1d. Only the LIVE slots are read: the reference zeroes all K columns of the slots >= num_points, so a pillar with
+ * num_points < T has relu(shift[c]) as a further candidate, added arithmetically (the padding slots may hold anything); a pillar
+ * with num_points == T has not. num_points == 0 (never produced by a voxelizer; NaN in the reference) gives relu(shift[c]).
+ * Outputs, either or both: feat (N_cap, channels); canvas (batch, channels, ny, nx) NCHW, CLEARED BY THE CALLER, column
+ * y * nx + x of frame b written. A pillar with b, y or x outside [0, batch) x [0, ny) x [0, nx) stores nothing on the canvas and
+ * sets *err_flag = 1 (device int32, may be NULL; zeroed by the caller).
+ * voxels == NULL: scatter alone -- feat (N_cap, channels) is the INPUT, canvas the output.
+ * SESSD_EINVAL before any launch: ndim != 4, channels != 64, T < 1, num_voxels_host < 0; with num_voxels_host > 0 also feat and
+ * canvas both NULL, a NULL input, a canvas with batch, ny or nx < 1. num_voxels_host == 0 launches nothing and reads no pointer. */
+int sessd_pillar_features(const float* voxels, const int32_t* num_points, const int32_t* coors, const int32_t* num_voxels_dev,
+                          int num_voxels_host, int max_points_per_voxel, int ndim, float vx, float vy, float x_offset,
+                          float y_offset, const float* weight, const float* scale, const float* shift, int channels,
+                          int with_distance, int batch, int ny, int nx, float* feat, float* canvas, int32_t* err_flag,
+                          sessd_stream_t stream);
 
 /* ------------------------------------------------------------------ iou3d_cuda operators (a15)
  * replace det3d/core/iou3d/src/iou3d.cpp:24-115 (boxes_overlap_bev_gpu, boxes_aligned_overlap_bev_gpu,

@@ -1,1 +1,2 @@
+from .point_pillars import PointPillars  # noqa: F401
 from .voxelnet import VoxelNet  # noqa: F401

@@ -31,6 +31,8 @@ class _Lowered:
             w = conv.weight.detach()
             if transposed_1x1:  # ConvTranspose2d(cin, cout, 1, stride=1): y[o] = sum_i x[i] W[i][o], a 1x1 conv with W transposed
                 pc = ops.pack_conv2d(w.transpose(0, 1).contiguous(), 1)
+            elif deconv and tuple(conv.kernel_size) == tuple(conv.stride) and conv.stride[0] == conv.stride[1] >= 2:
+                pc = ops.pack_deconv2d_ks(w, conv.stride[0])  # ConvTranspose2d(cin, cout, s, stride=s): s * s one-tap launches
             else:
                 pc = ops.pack_deconv2d_s2(w) if deconv else ops.pack_conv2d(w, conv.stride[0])
             if bn is not None:
@@ -174,7 +176,8 @@ class RPN(nn.Module):
     outputs concatenated. The up-sampler of an integer stride s >= 1 is ConvTranspose2d(cin, cout, s, stride=s) as in the reference
     (s = 1, the three-class config: a 1x1 conv with the weight transposed, lowered through the 1x1 kernels); a stride below 1 is a
     strided Conv2d (not in the reference at this commit). Lowered: stride-1/2 3x3 convs, 1x1 convs, the k = 1 stride-1 transposed
-    conv; a transposed up-sampler of stride >= 2 runs in plain torch."""
+    conv, and the k = s transposed up-samplers of stride s >= 2 (s * s output-parity launches of one tap each,
+    ops.pack_deconv2d_ks)."""
 
     def __init__(self, layer_nums, ds_layer_strides, ds_num_filters, us_layer_strides, us_num_filters,
                  num_input_features, norm_cfg=None, name="rpn", logger=None, **kwargs):
@@ -219,9 +222,5 @@ class RPN(nn.Module):
         for i in range(len(self.blocks)):
             x = _run_block(self._low, "blk%d" % i, self.blocks[i], x)
             if i - self._upsample_start_idx >= 0:
-                de = self.deblocks[i - self._upsample_start_idx]
-                if isinstance(de[0], nn.ConvTranspose2d) and tuple(de[0].stride) != (1, 1):
-                    ups.append(de(x))  # k == stride >= 2 transposed conv: plain torch (not on the SE-SSD path)
-                else:
-                    ups.append(_run_block(self._low, "de%d" % i, de, x))
+                ups.append(_run_block(self._low, "de%d" % i, self.deblocks[i - self._upsample_start_idx], x))
         return torch.cat(ups, dim=1) if len(ups) > 0 else x

@@ -72,6 +72,32 @@ VOXEL_GENERATOR = dict(range=[0, -40.0, -3.0, 70.4, 40.0, 1.0], voxel_size=[0.05
                        max_voxel_num=20000)
 
 
+def kitti_pointpillars_model():
+    """The model dict of the reference's PointPillars config (examples/point_pillars/configs/original_pp_mghead_syncbn_kitti.py:
+    42-93): PillarFeatureNet (one 64-filter PFN layer; voxel_size / pc_range not passed -- the reader's defaults apply) ->
+    PointPillarsScatter -> RPN with three blocks and up-samplers of stride 1 / 2 / 4 -> one Car task on 384 channels.
+    Inference only, through the det3d mirror."""
+    m = kitti_car_model()
+    m["type"] = "PointPillars"
+    m["reader"] = dict(type="PillarFeatureNet", num_filters=[64], with_distance=False, norm_cfg=None)
+    m["backbone"] = dict(type="PointPillarsScatter", ds_factor=1, norm_cfg=None)
+    m["neck"] = dict(type="RPN", layer_nums=[3, 5, 5], ds_layer_strides=[2, 2, 2], ds_num_filters=[64, 128, 256],
+                     us_layer_strides=[1, 2, 4], us_num_filters=[128, 128, 128], num_input_features=64, norm_cfg=None,
+                     logger=logging.getLogger("RPN"))
+    m["bbox_head"]["in_channels"] = sum([128, 128, 128])
+    m["bbox_head"]["weights"] = [1]
+    return m
+
+
+# test_cfg :104-115 and voxel_generator :166-171 of the same file
+TEST_CFG_POINTPILLARS = dict(nms=dict(use_rotate_nms=True, use_multi_class_nms=False, nms_pre_max_size=1000, nms_post_max_size=300,
+                                      nms_iou_threshold=0.5),
+                             score_threshold=0.05, post_center_limit_range=[0, -40.0, -5.0, 70.4, 40.0, 5.0], max_per_img=100)
+
+VOXEL_GENERATOR_POINTPILLARS = dict(range=[0, -39.68, -3, 69.12, 39.68, 1], voxel_size=[0.16, 0.16, 4.0], max_points_in_voxel=100,
+                                    max_voxel_num=12000)
+
+
 def build_synthetic_detector(device, seed=0, calib_frame_seed=0, max_voxels=16000, num_points=20000, supersample=1,
                              model_cfg=None, voxel_range=None):
     """det3d-mirror VoxelNet with seeded weights, BatchNorm statistics calibrated on one synthetic frame (on `device`) of the

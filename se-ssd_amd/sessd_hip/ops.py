@@ -241,6 +241,74 @@ def vfe_mean(voxels, num_points, num_features=4, num_voxels_dev=None):
     return out
 
 
+PILLAR_CHANNELS = 64   # sessd_pillar_features: one lane per output channel
+
+
+def fill_zero(t):
+    """Clear a contiguous float32 tensor with the library's own fill (a kernel launch, not a memset node)."""
+    if t.numel() == 0:
+        return t
+    assert t.is_contiguous() and t.data_ptr() % 16 == 0
+    check(lib.sessd_fill_u32(t.data_ptr(), 0, t.numel(), _stream()), "fill_u32")
+    return t
+
+
+def pillar_features(voxels, num_points, coors, weight, scale, shift, vx, vy, x_offset, y_offset, with_distance=False,
+                    num_voxels_dev=None, canvas=None, err_flag=None):
+    """PillarFeatureNet with one PFNLayer in eval mode (sessd_pillar_features): voxels (N, T, 4), num_points (N) int32, coors (N, 4)
+    int32 [b, z, y, x], weight (64, 9 | 10) as nn.Linear stores it, scale / shift (64) the folded BatchNorm1d -> (N, 64).
+    num_voxels_dev: device int32 live count (rows beyond it are not written). canvas (B, 64, ny, nx), cleared by the caller: the
+    pillars' columns are written in the same launch; err_flag (device int32[1], zeroed by the caller) is set when a pillar's cell
+    is outside it."""
+    _req(voxels, torch.float32, "voxels")
+    _req(num_points, torch.int32, "num_points")
+    _req(coors, torch.int32, "coors")
+    _req(weight, torch.float32, "weight")
+    _req(scale, torch.float32, "scale")
+    _req(shift, torch.float32, "shift")
+    N, T, ndim = voxels.shape
+    C, K = weight.shape
+    if K != (10 if with_distance else 9) or scale.numel() != C or shift.numel() != C:
+        raise ValueError("pillar_features: weight (C, %d), scale (C), shift (C) expected" % (10 if with_distance else 9))
+    if num_points.numel() != N or tuple(coors.shape) != (N, 4):
+        raise ValueError("pillar_features: num_points (N), coors (N, 4) expected")
+    B = ny = nx = 0
+    if canvas is not None:
+        _req(canvas, torch.float32, "canvas")
+        B, cc, ny, nx = canvas.shape
+        if cc != C:
+            raise ValueError("pillar_features: canvas must have %d channels" % C)
+    if err_flag is not None:
+        _req(err_flag, torch.int32, "err_flag")
+    if num_voxels_dev is not None:
+        _req(num_voxels_dev, torch.int32, "num_voxels_dev")
+    feat = torch.empty((N, C), dtype=torch.float32, device=voxels.device)
+    if N == 0:   # no pillars: nothing to launch (an empty tensor's pointer is null, which the entry point reads as "absent")
+        return feat
+    check(lib.sessd_pillar_features(voxels.data_ptr(), num_points.data_ptr(), coors.data_ptr(), _p(num_voxels_dev), N, T, ndim,
+                                    float(vx), float(vy), float(x_offset), float(y_offset), weight.data_ptr(), scale.data_ptr(),
+                                    shift.data_ptr(), C, 1 if with_distance else 0, B, ny, nx, feat.data_ptr(), _p(canvas),
+                                    _p(err_flag), _stream()), "pillar_features")
+    return feat
+
+
+def pillar_scatter(feat, coors, batch, ny, nx, num_voxels_dev=None, err_flag=None):
+    """PointPillarsScatter: feat (N, 64), coors (N, 4) int32 [b, z, y, x] -> (batch, 64, ny, nx), zero where no pillar lies (cleared
+    by sessd_fill_u32, then the scatter-alone form of sessd_pillar_features)."""
+    _req(feat, torch.float32, "feat")
+    _req(coors, torch.int32, "coors")
+    N, C = feat.shape
+    if tuple(coors.shape) != (N, 4):
+        raise ValueError("pillar_scatter: coors (N, 4) expected")
+    canvas = fill_zero(torch.empty((int(batch), C, int(ny), int(nx)), dtype=torch.float32, device=feat.device))
+    if N == 0:
+        return canvas
+    check(lib.sessd_pillar_features(0, 0, coors.data_ptr(), _p(num_voxels_dev), N, 1, 4, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, C, 0,
+                                    int(batch), int(ny), int(nx), feat.data_ptr(), canvas.data_ptr(), _p(err_flag), _stream()),
+          "pillar_scatter")
+    return canvas
+
+
 # ------------------------------------------------------------------ iou3d operators
 def boxes_pairwise(mode, a, b, out=None):
     w = 7 if mode in (2, 3) else 5
@@ -1652,6 +1720,26 @@ def pack_deconv2d_s2(weight):
     return pc
 
 
+def pack_deconv2d_ks(weight, s):
+    """nn.ConvTranspose2d(Cin, Cout, s, stride=s, bias=False) weight (Cin, Cout, s, s), s >= 2 (the RPN's up-samplers): kernel size
+    = stride, so every output pixel has ONE input pixel and one tap -- out(s y + py, s x + px) = W[:, :, py, px]^T in(y, x): s * s
+    output-parity launches of one tap each (dy = dx = 0, out_mul = s), packed straight from the stored tensor."""
+    w = weight.detach().to(torch.float32).contiguous()
+    ci, co, kh, kw = w.shape
+    s = int(s)
+    assert s >= 2 and kh == s and kw == s and ci % 2 == 0
+    zero = torch.zeros(1, dtype=torch.int32)
+    launches = []
+    for py in range(s):
+        for px in range(s):
+            # output channel o has element stride s * s, input channel c stride co * s * s, tap (py, px) offset py * s + px
+            offs = [py * s + px]
+            wpk = _pack_taps_view(w, s * s, co * s * s, offs, co, ci)
+            launches.append(dict(wpk=wpk, dy=zero, dx=zero, in_mul=1, out_mul=s, py=py, px=px, ntaps=1,
+                                 view=(w, s * s, co * s * s, offs)))
+    return PackedConv(launches, ci, co, "deconv_ks", s)
+
+
 def deconv2d_s2_pair(x, pc_a, pc_b, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a=None, residual_b=None, tile_cfg=4):
     """Two ConvTranspose2d(3, 2, 1, 1) layers of one shape on the SAME input in one launch (sessd_deconv2d_s2_mfma_pair); the same
     bits as two conv2d() calls with that tile_cfg (3, 4, 11 or 12)."""
@@ -1676,6 +1764,11 @@ def conv2d(x, pc, scale=None, shift=None, relu=True, residual=None, out=None, ti
     if pc.kind == "conv":
         Ho, Wo = (H + pc.stride - 1) // pc.stride, (W + pc.stride - 1) // pc.stride
         th, tw = Ho, Wo
+    elif pc.kind == "deconv_ks":   # kernel size = stride transposed conv: s * s one-tap launches of sessd_conv2d_mfma
+        if tile_cfg is not None and tile_cfg >= 20:
+            raise ValueError("a kernel-size = stride transposed conv runs on the sessd_conv2d_mfma tilings only")
+        Ho, Wo = pc.stride * H, pc.stride * W
+        th, tw = H, W
     else:
         Ho, Wo = 2 * H, 2 * W
         th, tw = H, W

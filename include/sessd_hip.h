@@ -104,6 +104,20 @@ int sessd_pillar_features(const float* voxels, const int32_t* num_points, const 
                           float y_offset, const float* weight, const float* scale, const float* shift, int channels,
                           int with_distance, int batch, int ny, int nx, float* feat, float* canvas, int32_t* err_flag,
                           sessd_stream_t stream);
+/* An up-sampler of the RPN neck straight into its channels of the concatenated map (csrc/deconv_ks.hip): replaces
+ * nn.ConvTranspose2d(cin, cout, s, stride=s, bias=False) + BatchNorm2d + ReLU (det3d/models/necks/rpn_v1.py:84-105) and the
+ * torch.cat of the up-samplers' outputs (:116), in ONE launch on the exact-f32 matrix cores:
+ *   out[b][c_off + o][s*y + py][s*x + px] = act(scale[o] * sum_i in[b][i][y][x] * W[i][o][py][px] + shift[o])
+ * in (batch, cin, hin, win); out (batch, c_total, s*hin, s*win), of which ONLY channels [c_off, c_off + cout) are written;
+ * wpk the weight (cin, cout, s, s) re-ordered as floats [py][cout / 32][cin / 2][px][cin parity][32 couts]
+ * (sessd_hip.ops.pack_deconv_ks_slice); scale / shift (cout) the folded BatchNorm, either may be NULL (1 / 0); relu != 0: max(., 0).
+ * Bit for bit an fmaf chain over cin in order, then fmaf(acc, scale, shift).
+ * SESSD_EINVAL before any launch: s not in {1, 2, 4}; cin odd or < 2; cout not a positive multiple of 32 (the kernel's cout
+ * block); c_off < 0 or c_off + cout > c_total; batch > 65535; one image's input or the packed weight of 2 GiB or more; and, for a
+ * non-empty call, a NULL in / wpk / out or an `out` not aligned to 4 * s bytes. batch * hin * win == 0 launches nothing: OK. */
+int sessd_deconv_ks_slice(const float* in, int batch, int cin, int hin, int win, const float* wpk, int s,
+                          float* out, int cout, int c_total, int c_off,
+                          const float* scale, const float* shift, int relu, sessd_stream_t stream);
 
 /* ------------------------------------------------------------------ iou3d_cuda operators (a15)
  * replace det3d/core/iou3d/src/iou3d.cpp:24-115 (boxes_overlap_bev_gpu, boxes_aligned_overlap_bev_gpu,

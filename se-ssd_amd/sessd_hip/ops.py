@@ -1740,6 +1740,56 @@ def pack_deconv2d_ks(weight, s):
     return PackedConv(launches, ci, co, "deconv_ks", s)
 
 
+class PackedDeconvKs:
+    """A kernel-size = stride transposed conv packed for sessd_deconv_ks_slice (pack_deconv_ks_slice)."""
+
+    def __init__(self, wpk, cin, cout, s):
+        self.wpk, self.cin, self.cout, self.stride, self.kind = wpk, cin, cout, s, "deconv_ks_slice"
+
+
+def pack_deconv_ks_slice(weight, s):
+    """nn.ConvTranspose2d(Cin, Cout, s, stride=s, bias=False) weight (Cin, Cout, s, s), s in {1, 2, 4}, Cin even, Cout % 32 == 0,
+    for the ONE-launch form sessd_deconv_ks_slice (csrc/deconv_ks.hip). Layout, floats:
+        [py][Cout / 32][Cin / 2][px][Cin parity][32 couts]     out[py][cb][kp][px][h][i] = W[2 kp + h][32 cb + i][py][px]
+    -- what a wave (one py, some cout blocks, all px) reads per k-step are adjacent 256-byte rows. A snapshot of the tensor as it
+    is now (a torch permute on the device, once per model): the engine that uses it is built from an eval-mode model and re-built
+    after a parameter write, so nothing is registered with the repack machinery."""
+    w = weight.detach().to(torch.float32).contiguous()
+    _req(w, torch.float32, "weight")
+    ci, co, kh, kw = w.shape
+    s = int(s)
+    if s not in (1, 2, 4) or kh != s or kw != s:
+        raise ValueError("pack_deconv_ks_slice: kernel size = stride in {1, 2, 4} expected, got kernel %dx%d, s = %d" % (kh, kw, s))
+    if ci % 2 or co % 32:
+        raise ValueError("pack_deconv_ks_slice: even cin and cout %% 32 == 0 expected, got %d -> %d" % (ci, co))
+    wpk = w.view(ci // 2, 2, co // 32, 32, s, s).permute(4, 2, 0, 5, 1, 3).contiguous()   # [kp, h, cb, i, py, px] -> [py, cb, kp, px, h, i]
+    return PackedDeconvKs(wpk, ci, co, s)
+
+
+def deconv_ks_slice(x, packed, scale, shift, relu, out, c_off):
+    """x (B, Cin, H, W) -> channels [c_off, c_off + Cout) of out (B, C_total, s*H, s*W), one launch (sessd_deconv_ks_slice):
+    ConvTranspose2d(Cin, Cout, s, stride=s) + folded BatchNorm (scale, shift: (Cout) or None) + ReLU. The rest of `out` is not
+    touched. Returns out."""
+    _req(x, torch.float32, "x")
+    _req(out, torch.float32, "out")
+    if scale is not None:
+        _req(scale, torch.float32, "scale")
+    if shift is not None:
+        _req(shift, torch.float32, "shift")
+    if x.dim() != 4 or out.dim() != 4:
+        raise ValueError("deconv_ks_slice: x (B, Cin, H, W) and out (B, C_total, s*H, s*W) expected")
+    B, ci, H, W = x.shape
+    s = packed.stride
+    if ci != packed.cin or out.shape[0] != B or out.shape[2] != s * H or out.shape[3] != s * W:
+        raise ValueError("deconv_ks_slice: x %s with cin %d, s = %d does not match out %s" % (tuple(x.shape), packed.cin, s, tuple(out.shape)))
+    if any(t is not None and t.numel() != packed.cout for t in (scale, shift)):
+        raise ValueError("deconv_ks_slice: scale / shift of %d elements expected" % packed.cout)
+    check(lib.sessd_deconv_ks_slice(x.data_ptr(), B, ci, H, W, packed.wpk.data_ptr(), s, out.data_ptr(), packed.cout,
+                                    int(out.shape[1]), int(c_off), _p(scale), _p(shift), 1 if relu else 0, _stream()),
+          "deconv_ks_slice")
+    return out
+
+
 def deconv2d_s2_pair(x, pc_a, pc_b, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a=None, residual_b=None, tile_cfg=4):
     """Two ConvTranspose2d(3, 2, 1, 1) layers of one shape on the SAME input in one launch (sessd_deconv2d_s2_mfma_pair); the same
     bits as two conv2d() calls with that tile_cfg (3, 4, 11 or 12)."""

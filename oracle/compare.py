@@ -25,6 +25,7 @@ Two rule sets (round-3 advisor finding: the relaxations made for the synthetic b
     frame's code scale x anchor size (the decode multiplies a box code's float32 error by the anchor diagonal; see RULES), at most
     10 decisions (1024 alternatives).
 The rule used is part of every result dict and of bench.py's `parity` object.
+compare_keep applies the same rule to a bare keep list of the rotated NMS (the stand-alone NMS entry points).
 """
 import itertools
 
@@ -52,8 +53,9 @@ RULES = {"strict": dict(relative_sizes=False, max_pairs=6, code_rtol=0.0),
 ANCHOR_CENTRE_SCALE = (float(np.hypot(1.6, 3.9)), float(np.hypot(1.6, 3.9)), 1.56)   # x, y: anchor diagonal; z: anchor height (config.py:64-70)
 
 
-def same_detections(got, want, box_tol=2e-3, score_rtol=1e-3, relative_sizes=False, code_rtol=0.0, code_scale=None):
+def same_detections(got, want, box_tol=2e-3, score_rtol=1e-3, relative_sizes=False, code_rtol=0.0, code_scale=None, score_atol=1e-6):
     """None if identical (count, order, values within tolerance), else a short description of the first difference.
+    Scores: |got - want| <= score_rtol * |want| + score_atol.
     code_rtol > 0 needs code_scale (the frame's debug dict: oracle/postprocess.py): without it the centre tolerance stays flat at box_tol."""
     gb, gs = np.asarray(got["box3d_lidar"], np.float32).reshape(-1, 7), np.asarray(got["scores"], np.float32)
     wb, ws = np.asarray(want["box3d_lidar"], np.float32).reshape(-1, 7), np.asarray(want["scores"], np.float32)
@@ -61,8 +63,8 @@ def same_detections(got, want, box_tol=2e-3, score_rtol=1e-3, relative_sizes=Fal
         return "count %d vs %d" % (len(gs), len(ws))
     if len(ws) == 0:
         return None
-    if not np.allclose(gs, ws, rtol=score_rtol, atol=1e-6):
-        k = int(np.argmax(np.abs(gs - ws) > score_rtol * np.abs(ws) + 1e-6))
+    if not np.allclose(gs, ws, rtol=score_rtol, atol=score_atol):
+        k = int(np.argmax(~(np.abs(gs - ws) <= score_rtol * np.abs(ws) + score_atol)))
         return "score of detection %d: %.6f vs %.6f" % (k, gs[k], ws[k])
     dpos = np.abs(gb[:, :3].astype(np.float64) - wb[:, :3])
     if code_rtol > 0 and code_scale is not None:
@@ -82,7 +84,7 @@ def same_detections(got, want, box_tol=2e-3, score_rtol=1e-3, relative_sizes=Fal
     return None
 
 
-def compare_detections(got, want, dbg, box_tol=2e-3, score_rtol=1e-3, max_pairs=None, rule="strict"):
+def compare_detections(got, want, dbg, box_tol=2e-3, score_rtol=1e-3, max_pairs=None, rule="strict", score_atol=1e-6):
     """got / want: dict(box3d_lidar (n,7), scores (n,), label_preds). dbg: the oracle's debug dict of the frame
     (oracle.pipeline.run_frames(return_intermediate=True)['debug'][b]; needs dbg['rerun'] when near pairs exist).
     Raises AssertionError on a mismatch; returns dict(n, matched, near_pairs, flipped) where `flipped` lists the
@@ -92,7 +94,7 @@ def compare_detections(got, want, dbg, box_tol=2e-3, score_rtol=1e-3, max_pairs=
     max_pairs = R["max_pairs"] if max_pairs is None else max_pairs
     pairs = np.asarray(dbg.get("near_pairs", np.zeros((0, 2), np.int64))).reshape(-1, 2)
     scale = dbg.get("code_scale")
-    why = same_detections(got, want, box_tol, score_rtol, rel, R["code_rtol"], scale)
+    why = same_detections(got, want, box_tol, score_rtol, rel, R["code_rtol"], scale, score_atol)
     n = len(np.asarray(want["scores"]))
     if why is None:
         return dict(n=n, matched=n, near_pairs=pairs.tolist(), flipped=[], rule=rule)
@@ -104,10 +106,44 @@ def compare_detections(got, want, dbg, box_tol=2e-3, score_rtol=1e-3, max_pairs=
     for flags in itertools.product((0, 1), repeat=len(pairs)):
         forced = [(int(i), int(j), int(f)) for (i, j), f in zip(pairs, flags)]
         alt = rerun(np.asarray(forced, np.int32))
-        w2 = same_detections(got, alt, box_tol, score_rtol, rel, R["code_rtol"], scale)
+        w2 = same_detections(got, alt, box_tol, score_rtol, rel, R["code_rtol"], scale, score_atol)
         if w2 is None:
             return dict(n=len(np.asarray(alt["scores"])), matched=len(np.asarray(alt["scores"])), near_pairs=pairs.tolist(), flipped=forced,
                         rule=rule)
         tried.append((flags, w2))
     raise AssertionError("detections match the oracle under NO assignment of its %d near-threshold decisions %s: baseline: %s; %s"
                          % (len(pairs), pairs.tolist(), why, "; ".join("%s -> %s" % t for t in tried[:8])))
+
+
+def compare_keep(got, dets, thresh, post_max=None, order=None, max_pairs=6):
+    """The same rule for a bare keep list of the rotated NMS. got: the kept indices as capi.rotate_nms_cc reports them (rows of
+    `dets` (K,6) [x,y,w,l,r,score]), already cut to post_max. It must equal rotate_nms_cc(dets, thresh, order)[0][:post_max], or
+    that call with ONE assignment of its listed near-threshold decisions (return_pairs) imposed through forced=; more than
+    `max_pairs` listed decisions is a failure. Raises AssertionError; returns dict(n, near_pairs, flipped)."""
+    from . import capi
+    got = np.asarray(got, np.int64).reshape(-1)
+    want, _, pairs = capi.rotate_nms_cc(dets, thresh, order=order, return_pairs=True)
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    want = want[:post_max]
+
+    def why(a, b):
+        if len(a) != len(b):
+            return "%d kept vs %d" % (len(a), len(b))
+        d = np.nonzero(a != b)[0]
+        return None if len(d) == 0 else "kept[%d] = %d vs %d" % (d[0], a[d[0]], b[d[0]])
+
+    w0 = why(got, want)
+    if w0 is None:
+        return dict(n=len(want), near_pairs=pairs.tolist(), flipped=[])
+    assert len(pairs) > 0, "keep lists differ (%s) and the oracle met no near-threshold NMS decision" % w0
+    assert len(pairs) <= max_pairs, "%d near-threshold decisions in one NMS problem: too many to call it comparable" % len(pairs)
+    tried = []
+    for flags in itertools.product((0, 1), repeat=len(pairs)):
+        forced = [(int(i), int(j), int(f)) for (i, j), f in zip(pairs, flags)]
+        alt = capi.rotate_nms_cc(dets, thresh, order=order, forced=np.asarray(forced, np.int32))[0][:post_max]
+        w2 = why(got, alt)
+        if w2 is None:
+            return dict(n=len(alt), near_pairs=pairs.tolist(), flipped=forced)
+        tried.append((flags, w2))
+    raise AssertionError("keep list matches the oracle under NO assignment of its %d near-threshold decisions %s: baseline: %s; %s"
+                         % (len(pairs), pairs.tolist(), w0, "; ".join("%s -> %s" % t for t in tried[:8])))

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import capi
+from oracle.compare import compare_keep
 from sessd_hip import synth
 
 pytestmark = pytest.mark.gpu
@@ -26,12 +26,13 @@ def test_rotate_nms_contract(dev, n, pre, post, thresh):
     k = n if pre is None else min(n, pre)
     sel = order[:k]
     dets = np.concatenate([b7[sel][:, [0, 1, 3, 4, 6]], scores[sel, None]], 1).astype(np.float32)
-    keep, near = capi.rotate_nms_cc(dets, thresh)
-    want = sel[keep[: (post if post is not None else len(keep))]]
-    if near == 0:
-        assert np.array_equal(got.cpu().numpy(), want)
-    else:
-        assert len(got) > 0
+    # identical, or the oracle under one assignment of its listed near-threshold decisions (oracle/compare.py); the oracle's
+    # keep list indexes `dets`, so the device's indices into the input are mapped back through `sel` (a permutation prefix)
+    got = got.cpu().numpy()
+    assert np.isin(got, sel).all() and len(np.unique(got)) == len(got)
+    pos = np.full(n, -1, np.int64)
+    pos[sel] = np.arange(k)
+    compare_keep(pos[got], dets, thresh, post_max=post)
 
 
 def test_axis_aligned_nms_contract(dev):

@@ -192,3 +192,84 @@ def test_strict_rule_allows_fewer_listed_decisions():
         compare_detections(got, want, dbg)                       # 8 listed decisions > 6
     with pytest.raises(AssertionError, match="NO assignment"):
         compare_detections(got, want, dbg, rule="synthetic")     # 8 <= 10: explored, and none matches
+
+
+# ---- compare_keep: the same rule for a bare keep list of the rotated NMS
+def _marginal_triples(m, thresh=0.3):
+    """m groups far apart, each three 2 x 2 axis-aligned boxes A > B > C in score: IoU(A, B) sits ON the threshold (one listed
+    decision per group), C overlaps B (IoU 1/3) and not A -- so C is kept exactly when the marginal decision suppresses B."""
+    dx = 2.0 - thresh * 8.0 / (1.0 + thresh) / 2.0
+    rows = []
+    for g in range(m):
+        x0 = 20.0 * g
+        for k, x in enumerate((x0, x0 + dx, x0 + dx + 1.0)):
+            rows.append([x, 0.0, 2.0, 2.0, 0.0, 0.9 - 0.01 * (3 * g + k)])
+    return np.asarray(rows, np.float32)
+
+
+def test_compare_keep_identical_passes_and_a_dropped_index_fails_without_near_pairs():
+    from oracle.compare import compare_keep
+    from sessd_hip import synth
+    d = synth.clustered_boxes7(300, seed=9)[:, [0, 1, 3, 4, 6]].astype(np.float32)
+    d = np.concatenate([d, np.linspace(0.95, 0.3, 300, dtype=np.float32)[:, None]], 1)
+    want, near, pairs = capi.rotate_nms_cc(d, 0.1, return_pairs=True)
+    assert near == 0 and len(pairs) == 0 and len(want) > 20
+    assert compare_keep(want, d, 0.1) == dict(n=len(want), near_pairs=[], flipped=[])
+    assert compare_keep(want[:10], d, 0.1, post_max=10)["n"] == 10
+    with pytest.raises(AssertionError, match="no near-threshold"):
+        compare_keep(np.delete(want, 5), d, 0.1)
+    with pytest.raises(AssertionError, match="no near-threshold"):
+        compare_keep(want[:9], d, 0.1, post_max=10)     # the whole list is compared, not a prefix
+    with pytest.raises(AssertionError, match="no near-threshold"):
+        compare_keep(want, d, 0.1, post_max=10)
+    # an explicit order is passed through: the reversed score order keeps other boxes
+    rev = np.arange(300, dtype=np.int32)[::-1].copy()
+    w2 = capi.rotate_nms_cc(d, 0.1, order=rev)[0]
+    assert not np.array_equal(w2, want) and compare_keep(w2, d, 0.1, order=rev)["flipped"] == []
+    with pytest.raises(AssertionError):
+        compare_keep(want, d, 0.1, order=rev)
+
+
+def test_compare_keep_accepts_only_an_assignment_of_the_listed_decisions():
+    from oracle.compare import compare_keep
+    d = _marginal_triples(2)
+    base, near, pairs = capi.rotate_nms_cc(d, 0.3, return_pairs=True)
+    assert near == 2 and pairs.tolist() == [[0, 1], [3, 4]]
+    assert compare_keep(base, d, 0.3)["flipped"] == []
+    for f0 in (0, 1):
+        for f1 in (0, 1):
+            forced = [(0, 1, f0), (3, 4, f1)]
+            alt = capi.rotate_nms_cc(d, 0.3, forced=np.asarray(forced, np.int32))[0]
+            assert alt.tolist() == [0, 2 if f0 else 1, 3, 5 if f1 else 4]
+            r = compare_keep(alt, d, 0.3)
+            assert r["flipped"] == ([] if np.array_equal(alt, base) else forced) and r["near_pairs"] == [[0, 1], [3, 4]]
+    for bad in ([0, 1, 2, 3, 4], [0, 3], [0, 1, 3], [1, 2, 3, 4], [0, 1, 4, 3]):   # no assignment gives these
+        with pytest.raises(AssertionError, match="NO assignment"):
+            compare_keep(np.asarray(bad), d, 0.3)
+    assert compare_keep([0], d, 0.3, post_max=1)["n"] == 1
+    with pytest.raises(AssertionError, match="NO assignment"):
+        compare_keep([1], d, 0.3, post_max=1)
+
+
+def test_compare_keep_rejects_too_many_listed_decisions():
+    from oracle.compare import compare_keep
+    d = _marginal_triples(7)
+    base, near, _ = capi.rotate_nms_cc(d, 0.3, return_pairs=True)
+    assert near == 7
+    assert compare_keep(base, d, 0.3)["flipped"] == []           # identical needs no excuse
+    flip = capi.rotate_nms_cc(d, 0.3, forced=np.array([[0, 1, 0]], np.int32))[0]
+    other = flip if not np.array_equal(flip, base) else capi.rotate_nms_cc(d, 0.3, forced=np.array([[0, 1, 1]], np.int32))[0]
+    with pytest.raises(AssertionError, match="too many"):
+        compare_keep(other, d, 0.3)                              # 7 listed decisions > 6
+    assert len(compare_keep(other, d, 0.3, max_pairs=7)["flipped"]) == 7
+
+
+def test_score_atol_is_a_parameter_of_the_rule():
+    want = dict(box3d_lidar=np.zeros((1, 7), np.float32), scores=np.array([1e-3], np.float32))
+    got = dict(box3d_lidar=np.zeros((1, 7), np.float32), scores=np.array([1e-3 + 5e-7], np.float32))
+    dbg = dict(near_pairs=np.zeros((0, 2), np.int64))
+    assert same_detections(got, want, score_rtol=1e-5) is None                    # default absolute term 1e-6
+    assert same_detections(got, want, score_rtol=1e-5, score_atol=1e-7) is not None
+    assert compare_detections(got, want, dbg, score_rtol=1e-5)["matched"] == 1
+    with pytest.raises(AssertionError):
+        compare_detections(got, want, dbg, score_rtol=1e-5, score_atol=1e-7)

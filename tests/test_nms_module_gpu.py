@@ -4,7 +4,7 @@ nms_cpu.h:24-70 written here. Index lists must be identical."""
 import numpy as np
 import pytest
 
-from oracle import capi
+from oracle.compare import compare_keep
 from sessd_hip import synth
 
 pytestmark = pytest.mark.gpu
@@ -67,11 +67,8 @@ def test_rotate_nms_cc_and_corner_entry(dev, n, thresh):
     rng = np.random.RandomState(n)
     dets = np.concatenate([b7[:, [0, 1, 3, 4, 6]], rng.permutation(n).astype(np.float32)[:, None] / max(n, 1)], 1).astype(np.float32)
     got = nms_cpu.rotate_nms_cc(dets, thresh)
-    want, near = capi.rotate_nms_cc(dets, thresh)
-    if near == 0:
-        assert list(got) == list(want)
-    else:  # a pair within the oracle's margin of the threshold may flip: same prefix up to the first difference is enough
-        assert len(got) > 0
+    # identical, or the oracle under one assignment of its listed near-threshold decisions (oracle/compare.py)
+    compare_keep(np.asarray(got, np.int64), dets, thresh)
     if n:
         order = dets[:, 5].argsort()[::-1].astype(np.int32)
         corners = box_np_ops.center_to_corner_box2d(dets[:, :2], dets[:, 2:4], dets[:, 4]).astype(np.float32)

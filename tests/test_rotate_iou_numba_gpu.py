@@ -35,18 +35,21 @@ def test_mirror_numpy_api(dev):
     assert iou.shape == (200, 200) and np.abs(iou - oracle.rotate_iou_eval(b, b, -1))[off].max() < 2e-5
     assert rotate_iou_gpu_eval(b[:0], b).shape == (0, 200)
     # rotate_nms_gpu: greedy on devRotateIoU > thresh over score order
+    # box seed 5 (seed 3 above has a pair 4.8e-5 from the threshold): the oracle matrix has no entry within 1e-4 of 0.3 -- the
+    # closest is 5.7e-4, thirty times the 2e-5 the device's IoU is held to -- so the keep list must be IDENTICAL
+    bn = _boxes(200, 5)
     rng = np.random.RandomState(0)
-    dets = np.concatenate([b, rng.rand(200, 1).astype(np.float32)], 1)
+    dets = np.concatenate([bn, rng.rand(200, 1).astype(np.float32)], 1)
     keep = rotate_nms_gpu(dets, 0.3)
     order = dets[:, 5].argsort()[::-1]
-    ref_iou = oracle.rotate_iou_eval(b[order], b[order], -1).T  # [i][j] = IoU(box_i, box_j) in sorted order
+    ref_iou = oracle.rotate_iou_eval(bn[order], bn[order], -1).T  # [i][j] = IoU(box_i, box_j) in sorted order
     alive, want = np.ones(200, bool), []
     for i in range(200):
         if alive[i]:
             want.append(order[i])
             alive[i + 1:] &= ~(ref_iou[i, i + 1:] > 0.3)
-    near = int((np.abs(ref_iou - 0.3) < 1e-4).sum())
-    assert list(keep) == want or near > 0
+    assert int((np.abs(ref_iou - 0.3) < 1e-4).sum()) == 0 and len(want) < 100
+    assert list(keep) == want
     # nms_gpu: axis aligned, +1 convention
     aa = np.stack([b[:, 0] * 10, b[:, 1] * 10 + 400, b[:, 0] * 10 + b[:, 2] * 12, b[:, 1] * 10 + 400 + b[:, 3] * 12, dets[:, 5]], 1).astype(np.float32)
     keep2 = nms_gpu(aa, 0.4)

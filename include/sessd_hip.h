@@ -104,6 +104,33 @@ int sessd_pillar_features(const float* voxels, const int32_t* num_points, const 
                           float y_offset, const float* weight, const float* scale, const float* shift, int channels,
                           int with_distance, int batch, int ny, int nx, float* feat, float* canvas, int32_t* err_flag,
                           sessd_stream_t stream);
+/* Staged clouds -> canvas without the (N, T, 4) tensor (csrc/pillar.hip): sessd_voxelize_frames + sessd_pillar_features as ONE call
+ * that never writes voxels / mean. The list fill and the insert, count and assign launches are sessd_voxelize_frames' own
+ * (points, hash, workspace, range, voxel size, grid, T and max_voxels arguments with its meaning; ndim must be 4; prefix[0] must be
+ * 0 on entry); a fifth launch, one wave per pillar and one grid row per frame, takes the place of the gather and of
+ * sessd_pillar_features: lane j of round r reads entry 64 r + j of the pillar's ascending point-index list, the entries below the
+ * frame's break index are the live points, each live lane loads its point from the staged cloud as one float4, and from there
+ * the arithmetic is sessd_pillar_features' (the same device function): every output equals, bit for bit, what
+ * sessd_voxelize_frames followed by sessd_pillar_features gives.
+ * Outputs: canvas (batch, channels, ny, nx), CLEARED BY THE CALLER, the pillars' columns only; coors (batch * max_voxels, 4)
+ * [b, z, y, x] and prefix (batch + 1) as sessd_voxelize_frames writes them; num_points (batch * max_voxels) and feat
+ * (batch * max_voxels, channels), either may be NULL; *err_flag (device int32, may be NULL, sticky) = 1 when a pillar's cell
+ * lies outside (ny, nx). Rows beyond prefix[batch] are not written.
+ * Measured on MI355X at full size (432 x 496 canvas, batch 1, a 20 000-point cloud = 4270 pillars, T = 100; hash clear and canvas
+ * clear included, a captured graph replayed back to back): 114 us against 173 us for sessd_voxelize_frames +
+ * sessd_pillar_features (profiles/pillar_front_end_fused.json).
+ * SESSD_EINVAL before any launch: ndim != 4, channels != 64, batch < 1 or > 65535, ny or nx < 1, points_per_frame, T or max_voxels
+ * < 1, a hash capacity that is not a power of two or < 2 * batch * points_per_frame, a NULL points / range / voxel size / grid /
+ * hash / weight / scale / shift / canvas / coors / prefix / workspace; SESSD_EWORKSPACE: workspace_bytes below
+ * sessd_pillar_frames_workspace_bytes (= sessd_voxelize_frames_workspace_bytes). */
+size_t sessd_pillar_frames_workspace_bytes(uint32_t hash_capacity, int batch, int points_per_frame, int max_points_per_voxel,
+                                           int max_voxels);
+int sessd_pillar_frames(const float* points, int batch, int points_per_frame, int ndim, const float* range6,
+                        const float* voxel_size3, const int32_t* grid3, int max_points_per_voxel, int max_voxels,
+                        uint32_t* hash_keys, int32_t* hash_vals, uint32_t hash_capacity, float vx, float vy, float x_offset,
+                        float y_offset, const float* weight, const float* scale, const float* shift, int channels,
+                        int with_distance, int ny, int nx, float* canvas, int32_t* coors, int32_t* prefix, int32_t* num_points,
+                        float* feat, int32_t* err_flag, void* workspace, size_t workspace_bytes, sessd_stream_t stream);
 /* An up-sampler of the RPN neck straight into its channels of the concatenated map (csrc/deconv_ks.hip): replaces
  * nn.ConvTranspose2d(cin, cout, s, stride=s, bias=False) + BatchNorm2d + ReLU (det3d/models/necks/rpn_v1.py:84-105) and the
  * torch.cat of the up-samplers' outputs (:116), in ONE launch on the exact-f32 matrix cores:

@@ -5,7 +5,8 @@ several rounds, medians reported (min / max beside them). Writes one JSON file (
   (a) time per frame of the module path (ops.voxelize_frames + the det3d-mirror PointPillars, its one read-back of the counts
       included), of PillarEngine.enqueue() eager, and of replay() -- with the one-launch up-samplers and with the module path's
       lowering (`fused_upsamplers = False`);
-  (b) PillarEngine.stage_times(): voxelize (with its hash and list clears), canvas_clear, pillar, blk<i>, up<i>, head, predict;
+  (b) PillarEngine.stage_times(): voxelize (with its hash and list clears), canvas_clear, pillar (the engine's default front end,
+      "fused", reports canvas_clear and front_end instead: scripts/pillar_front_end_probe.py), blk<i>, up<i>, head, predict;
   (c) every up-sampler alone on the frame's own block outputs: sessd_deconv_ks_slice against the module path's lowering
       (s * s one-tap launches into a scratch map) + the copy into the slice, interleaved.
 Before any timing the outputs are compared: the parent-lowering engine against the module path (bit for bit) and the fused head map

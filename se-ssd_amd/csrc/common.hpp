@@ -48,6 +48,20 @@ int sessd_external_clear_enabled();
     if (!sessd_external_clear_enabled()) SESSD_FILL(ptr, value, n_words, stream); \
   } while (0)
 
+// The voxelizer's launches up to the voxel assignment (voxelize.hip): argument checks, list fill, insert, count, assign -- all
+// frames of a batch. Shared by sessd_voxelize_frames (which gathers the (N, T, ndim) tensor next) and sessd_pillar_frames
+// (pillar.hip, which reads the lists itself). `state` receives where the per-cell lists, the voxel -> hash entry table
+// (batch, max_voxels) and the per-frame words meta (batch, 4) [cut, unique cells, -, -] lie in the workspace.
+struct SessdVoxState {
+  const int* lists;
+  const int* entry_of_vid;
+  const int* meta;
+};
+int sessd_voxelize_front(const float* points, int batch, int points_per_frame, int ndim, const float* range6,
+                         const float* voxel_size3, const int* grid3, int max_points_per_voxel, int max_voxels, uint32_t* hash_keys,
+                         int* hash_vals, uint32_t hash_capacity, int* coors, int coors_stride, int* prefix, void* workspace,
+                         size_t workspace_bytes, hipStream_t stream, SessdVoxState* state);
+
 static inline __host__ __device__ int sessd_divup(int a, int b) { return (a + b - 1) / b; }
 static inline __host__ __device__ size_t sessd_align(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

@@ -399,6 +399,35 @@ int sessd_voxelize_frames(const float* points, int batch, int points_per_frame, 
                           uint32_t* hash_keys, int* hash_vals, uint32_t hash_capacity, float* voxels, int* coors, int coors_stride,
                           int* num_points_per_voxel, float* mean_feat, int* prefix, void* workspace, size_t workspace_bytes,
                           hipStream_t stream) {
+  SessdVoxState st;
+  const int rc = sessd_voxelize_front(points, batch, points_per_frame, ndim, range6, voxel_size3, grid3, max_points_per_voxel,
+                                      max_voxels, hash_keys, hash_vals, hash_capacity, coors, coors_stride, prefix, workspace,
+                                      workspace_bytes, stream, &st);
+  if (rc != SESSD_OK) return rc;
+  const int MP = max_points_per_voxel, P = points_per_frame;
+  const int gblk = sessd_divup(max_voxels < P ? max_voxels : P, VOX_NT);
+  if (ndim == 4)
+    SESSD_LAUNCH(vox_gather_kernel<4>, dim3(gblk, batch), dim3(VOX_NT), 0, stream, points, ndim, st.lists, MP, st.entry_of_vid, st.meta,
+                 max_voxels, prefix, voxels, num_points_per_voxel, mean_feat, P);
+  else
+    SESSD_LAUNCH(vox_gather_kernel<0>, dim3(gblk, batch), dim3(VOX_NT), 0, stream, points, ndim, st.lists, MP, st.entry_of_vid, st.meta,
+                 max_voxels, prefix, voxels, num_points_per_voxel, mean_feat, P);
+  SESSD_CHECK_LAUNCH();
+  return SESSD_OK;
+}
+
+size_t sessd_pillar_frames_workspace_bytes(uint32_t hash_capacity, int batch, int points_per_frame, int max_points_per_voxel,
+                                           int max_voxels) {
+  return sessd_voxelize_frames_workspace_bytes(hash_capacity, batch, points_per_frame, max_points_per_voxel, max_voxels);
+}
+
+}  // extern "C"
+
+// list fill + insert + count + assign of all frames: the launches sessd_voxelize_frames and sessd_pillar_frames share
+int sessd_voxelize_front(const float* points, int batch, int points_per_frame, int ndim, const float* range6,
+                         const float* voxel_size3, const int* grid3, int max_points_per_voxel, int max_voxels, uint32_t* hash_keys,
+                         int* hash_vals, uint32_t hash_capacity, int* coors, int coors_stride, int* prefix, void* workspace,
+                         size_t workspace_bytes, hipStream_t stream, SessdVoxState* state) {
   if (batch < 1 || batch > 65535 || points_per_frame < 1 || ndim < 3 || ndim > 8 || max_points_per_voxel < 1 || max_voxels < 1)
     return SESSD_EINVAL;
   if (coors_stride != 3 && coors_stride != 4) return SESSD_EINVAL;
@@ -426,16 +455,13 @@ int sessd_voxelize_frames(const float* points, int batch, int points_per_frame, 
   SESSD_LAUNCH(vox_assign_kernel, dim3(nblk, batch), dim3(VOX_NT), 0, stream, P, w.ent, w.lists, MP, w.blk_cnt, nblk, hash_keys, 0u, G,
                max_voxels, 0, prefix, hash_vals, w.entry_of_vid, coors, coors_stride, w.meta, prefix + 1, (uint32_t)cells, 1);
   SESSD_CHECK_LAUNCH();
-  const int gblk = sessd_divup(max_voxels < P ? max_voxels : P, VOX_NT);
-  if (ndim == 4)
-    SESSD_LAUNCH(vox_gather_kernel<4>, dim3(gblk, batch), dim3(VOX_NT), 0, stream, points, ndim, w.lists, MP, w.entry_of_vid, w.meta,
-                 max_voxels, prefix, voxels, num_points_per_voxel, mean_feat, P);
-  else
-    SESSD_LAUNCH(vox_gather_kernel<0>, dim3(gblk, batch), dim3(VOX_NT), 0, stream, points, ndim, w.lists, MP, w.entry_of_vid, w.meta,
-                 max_voxels, prefix, voxels, num_points_per_voxel, mean_feat, P);
-  SESSD_CHECK_LAUNCH();
+  state->lists = w.lists;
+  state->entry_of_vid = w.entry_of_vid;
+  state->meta = w.meta;
   return SESSD_OK;
 }
+
+extern "C" {
 
 // points (n,4) float32 -> dst (capacity,4): copy + out-of-range padding, one launch on `stream`.
 int sessd_stage_points(const float* points, int num_points, float* dst, int capacity, hipStream_t stream) {

@@ -84,7 +84,10 @@ SIGNATURES = {
     "sessd_voxelize_frames": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, u32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
     "sessd_vfe_mean": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "sessd_pillar_features": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
-    "sessd_deconv_ks_slice": (i32, [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp]),
+    "sessd_pillar_frames_workspace_bytes": (sz, [u32, i32, i32, i32, i32]),
+    "sessd_pillar_frames": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, u32, f32, f32, f32, f32, vp, vp, vp, i32, i32, i32, i32,
+                                  vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "sessd_deconv_ks_slice":(i32, [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp]),
     "sessd_boxes_pairwise": (i32, [i32, vp, i32, vp, i32, vp, vp]),
     "sessd_boxes_aligned_overlap_bev": (i32, [vp, vp, i32, vp, vp]),
     "sessd_rotate_iou_eval": (i32, [vp, i32, vp, i32, i32, vp, vp]),

@@ -292,6 +292,82 @@ def pillar_features(voxels, num_points, coors, weight, scale, shift, vx, vy, x_o
     return feat
 
 
+_byte_workspace = workspace   # (pillar_frames has a `workspace` argument of its own)
+
+
+def pillar_frames(points, voxel_size, coors_range, max_points, max_voxels, weight, scale, shift, vx, vy, x_offset, y_offset,
+                  with_distance=False, canvas=None, err_flag=None, hash=None, workspace=None, prefix=None, coors=None,
+                  num_points=None, feat=None):
+    """Clouds -> canvas in one call (sessd_pillar_frames): voxelize_frames + pillar_features(canvas=) without the (N, T, 4) tensor,
+    the same bits. points: a list of (P_i, 4) float32 device clouds (staged here, shorter ones padded with out-of-range rows) or a
+    staged (B, P, 4) tensor. weight (64, 9 | 10), scale / shift (64), vx .. y_offset: as pillar_features. What is not given is
+    allocated, and cleared where the entry point wants it cleared: canvas (B, 64, ny, nx) of the voxel grid (a given canvas is the
+    caller's to clear, as is a given err_flag), hash (a VoxelHash over B * P items; a given one is cleared here, every call),
+    workspace (bytes), prefix (B + 1, prefix[0] = 0), coors (B * max_voxels, 4), num_points (B * max_voxels), feat
+    (B * max_voxels, 64). Returns dict(canvas, prefix, coors, num_points, feat); rows beyond prefix[B] are unspecified."""
+    staged = points
+    if isinstance(points, (list, tuple)):
+        for p in points:
+            _req(p, torch.float32, "points")
+            if p.dim() != 2 or p.shape[1] != 4:
+                raise ValueError("pillar_frames: every cloud must be (P, 4) [x, y, z, r]")
+        dev = points[0].device
+        B, P = len(points), max(1, max(int(p.shape[0]) for p in points))
+        staged = torch.empty((B, P, 4), dtype=torch.float32, device=dev)
+        for b, p in enumerate(points):
+            check(lib.sessd_stage_points(p.data_ptr(), p.shape[0], staged[b].data_ptr(), P, _stream()), "stage_points")
+    _req(staged, torch.float32, "points")
+    if staged.dim() != 3 or staged.shape[2] != 4 or staged.shape[0] < 1 or staged.shape[1] < 1:
+        raise ValueError("pillar_frames: staged points must be (B, P, 4) with B, P >= 1")
+    for t, name in ((weight, "weight"), (scale, "scale"), (shift, "shift")):
+        _req(t, torch.float32, name)
+    dev = staged.device
+    B, P = int(staged.shape[0]), int(staged.shape[1])
+    C, K = weight.shape
+    if C != PILLAR_CHANNELS or K != (10 if with_distance else 9) or scale.numel() != C or shift.numel() != C:
+        raise ValueError("pillar_frames: weight (%d, %d), scale (%d), shift (%d) expected" % (PILLAR_CHANNELS, 10 if with_distance else 9,
+                                                                                            PILLAR_CHANNELS, PILLAR_CHANNELS))
+    vs = torch.tensor(voxel_size, dtype=torch.float32)
+    cr = torch.tensor(coors_range, dtype=torch.float32)
+    grid = torch.round((cr[3:] - cr[:3]) / vs).to(torch.int32)
+    cap = B * int(max_voxels)
+    if canvas is None:
+        canvas = fill_zero(torch.empty((B, C, int(grid[1]), int(grid[0])), dtype=torch.float32, device=dev))
+    _req(canvas, torch.float32, "canvas")
+    if canvas.dim() != 4 or canvas.shape[0] != B or canvas.shape[1] != C:
+        raise ValueError("pillar_frames: canvas must be (%d, %d, ny, nx)" % (B, C))
+    ny, nx = int(canvas.shape[2]), int(canvas.shape[3])
+    if hash is None:
+        hash = VoxelHash(P * B, dev)
+    hash.clear()
+    need = int(lib.sessd_pillar_frames_workspace_bytes(hash.capacity, B, P, int(max_points), int(max_voxels)))
+    if workspace is None:
+        workspace = _byte_workspace(need, dev, "pillar_frames")
+    if prefix is None:
+        prefix = torch.zeros((B + 1,), dtype=torch.int32, device=dev)
+    if coors is None:
+        coors = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+    if num_points is None:
+        num_points = torch.empty((cap,), dtype=torch.int32, device=dev)
+    if feat is None:
+        feat = torch.empty((cap, C), dtype=torch.float32, device=dev)
+    for t, dt, name, n in ((workspace, torch.uint8, "workspace", need), (prefix, torch.int32, "prefix", B + 1),
+                           (coors, torch.int32, "coors", cap * 4), (num_points, torch.int32, "num_points", cap),
+                           (feat, torch.float32, "feat", cap * C)):
+        _req(t, dt, name)
+        if t.numel() < n:
+            raise ValueError("pillar_frames: %s holds %d elements, %d needed" % (name, t.numel(), n))
+    if err_flag is not None:
+        _req(err_flag, torch.int32, "err_flag")
+    check(lib.sessd_pillar_frames(staged.data_ptr(), B, P, 4, cr.data_ptr(), vs.data_ptr(), grid.data_ptr(), int(max_points),
+                                  int(max_voxels), hash.keys.data_ptr(), hash.vals.data_ptr(), hash.capacity, float(vx), float(vy),
+                                  float(x_offset), float(y_offset), weight.data_ptr(), scale.data_ptr(), shift.data_ptr(), C,
+                                  1 if with_distance else 0, ny, nx, canvas.data_ptr(), coors.data_ptr(), prefix.data_ptr(),
+                                  num_points.data_ptr(), feat.data_ptr(), _p(err_flag), workspace.data_ptr(), workspace.numel(),
+                                  _stream()), "pillar_frames")
+    return dict(canvas=canvas, prefix=prefix, coors=coors, num_points=num_points, feat=feat)
+
+
 def pillar_scatter(feat, coors, batch, ny, nx, num_voxels_dev=None, err_flag=None):
     """PointPillarsScatter: feat (N, 64), coors (N, 4) int32 [b, z, y, x] -> (batch, 64, ny, nx), zero where no pillar lies (cleared
     by sessd_fill_u32, then the scatter-alone form of sessd_pillar_features)."""

@@ -13,7 +13,15 @@ torch.cat the up-samplers' outputs -- each up-sampler is ONE launch of sessd_dec
 instead (ops.pack_deconv2d_ks: s * s one-tap launches into a scratch map, + a copy into the slice): for A/B runs and for the
 bit-equality test against the module path.
 
-Not here: multi-task heads, records rings, the runner, tile lists, training."""
+The front end (clouds -> canvas) has two forms, `front_end=`: "tensor" = sessd_voxelize_frames, which writes the (N, T, 4) pillar
+tensor, then sessd_pillar_features, which reads its live slots; "fused" = sessd_pillar_frames, the same insert / count / assign
+launches followed by ONE wave-per-pillar launch that reads the voxelizer's index lists and the staged cloud itself -- the same bits
+on the canvas, no pillar tensor. DEFAULT_FRONT_END is what scripts/pillar_engine_probe.py measured faster.
+
+For runner.HostFedPipeline / runner.pillar_engines_on_cu_sets the engine has InferenceEngine's runner surface: attach_records()
+(a device ring the frame's last launch appends its detections to), num_tasks, nms_truncated, cu_budget, err_text.
+
+Not here: multi-task heads, tile lists, training."""
 import numpy as np
 import torch
 from torch import nn
@@ -23,6 +31,8 @@ from . import ops
 from .engine import fold_bn, _round_up
 
 UP_STRIDES = (1, 2, 4)   # sessd_deconv_ks_slice
+FRONT_ENDS = ("fused", "tensor")
+DEFAULT_FRONT_END = "fused"
 
 
 def _block_layers(block, i):
@@ -119,10 +129,14 @@ def check_pillar_model(model, canvas_hw=None):
 
 
 class PillarEngine:
-    def __init__(self, model, voxel_generator_cfg, test_cfg, batch_size=1, max_points=32768, anchors=None, device=None):
+    num_tasks = 1   # one head task (check_pillar_model): a frame's record holds post_max rows
+
+    def __init__(self, model, voxel_generator_cfg, test_cfg, batch_size=1, max_points=32768, anchors=None, device=None,
+                 front_end=None):
         """model: the mirror's PointPillars, eval mode, on the device. voxel_generator_cfg: range, voxel_size, max_points_in_voxel,
         max_voxel_num (configs.VOXEL_GENERATOR_POINTPILLARS). max_points: capacity of a frame's cloud. anchors: (A, 7) or
-        (B, A, 7), A = 2 * H' * W'; None = the anchors of the head's class (configs.KITTI_3CLASS_ANCHORS) over the voxel range."""
+        (B, A, 7), A = 2 * H' * W'; None = the anchors of the head's class (configs.KITTI_3CLASS_ANCHORS) over the voxel range.
+        front_end: "fused" | "tensor" (module docstring); None = DEFAULT_FRONT_END."""
         nms = test_cfg["nms"] if isinstance(test_cfg, dict) else test_cfg.nms
         self.pre_max, self.post_max = int(nms["nms_pre_max_size"]), int(nms["nms_post_max_size"])
         self.nms_thresh = float(nms["nms_iou_threshold"])
@@ -133,6 +147,9 @@ class PillarEngine:
         self.grid = torch.round((self.vrange[3:] - self.vrange[:3]) / self.vsize).to(torch.int32)   # x, y, z
         nx, ny = int(self.grid[0]), int(self.grid[1])
         parts = check_pillar_model(model, (ny, nx))
+        self.front_end = DEFAULT_FRONT_END if front_end is None else front_end
+        if self.front_end not in FRONT_ENDS:
+            raise ValueError("PillarEngine: front_end must be one of %s, got %r" % (FRONT_ENDS, front_end))
         self.dev = dev = next(model.parameters()).device if device is None else device
         if dev.type != "cuda":
             raise ValueError("PillarEngine needs the model on the HIP device: there is no CPU fallback")
@@ -154,12 +171,15 @@ class PillarEngine:
         self.points = torch.full((B, self.P_cap, 4), -1.0e6, dtype=f32, device=dev)   # padded rows fall out of range
         self.hash = ops.VoxelHash(self.P_cap * B, dev)
         cap = self.cap = B * self.max_voxels
-        self.voxels, self.coors, self.nump, self.mean = E(cap, self.T, 4), E(cap, 4, dt=i32), E(cap, dt=i32), E(cap, 4)
+        self.coors, self.nump = E(cap, 4, dt=i32), E(cap, dt=i32)
+        # the (N, T, 4) pillar tensor and the mean rows: the tensor front end's alone
+        self.voxels, self.mean = (E(cap, self.T, 4), E(cap, 4)) if self.front_end == "tensor" else (None, None)
         self.prefix = torch.zeros((B + 1,), dtype=i32, device=dev)   # prefix[0] stays 0; [1 .. B] written by every frame
         self.vox_ws = torch.empty(int(lib.sessd_voxelize_frames_workspace_bytes(self.hash.capacity, B, self.P_cap, self.T, self.max_voxels)),
                                   dtype=torch.uint8, device=dev)
         # a pillar outside the canvas: STICKY across frames (the kernel only ever sets it); results() reports and re-arms it
         self.err = torch.zeros((1,), dtype=i32, device=dev)
+        self.err_text = "a pillar's cell lies outside the %d x %d canvas: voxel range and canvas do not match" % (ny, nx)
         self.canvas = torch.zeros((B, ops.PILLAR_CHANNELS, ny, nx), dtype=f32, device=dev)
         # ---- neck: the packers and default tile_cfg choices of RPN.forward / _run_block
         self.blocks, self.ups = [], []
@@ -213,8 +233,30 @@ class PillarEngine:
         if self.nms_type == "rotate_weighted_nms":   # the layout ops.predict returns for DI-NMS (one task)
             self.out.update(task_count=torch.zeros((B, 1), dtype=i32, device=dev), di_truncated=torch.zeros((B, 1), dtype=i32, device=dev),
                             di_keep=torch.zeros((B, 1, post), dtype=i32, device=dev), di_keep_count=torch.zeros((B, 1), dtype=i32, device=dev))
+        # the STICKY OR of DI-NMS's di_truncated over all frames so far (outside every per-frame clear, like self.err; nothing raises)
+        self.nms_truncated = torch.zeros((1,), dtype=i32, device=dev)
+        self._pred_out = dict(self.out, di_truncated_sticky=self.nms_truncated) if self.nms_type == "rotate_weighted_nms" else self.out
+        # compute units this engine's stream may use (0 = the whole chip): sizes the persistent launches of ops.conv2d
+        self.cu_budget = 0
+        self.records = self.record_counts = self.record_cursor = None
         self.graph = None
         self._marks = None
+
+    def attach_records(self, capacity_frames):
+        """Keep every frame's detections on the device as a fixed-size record (capacity_frames, post_max, 9) [box 7 | score | label]
+        + counts, appended by the frame's own last launch (also inside a captured graph, hence before capture())."""
+        if self.graph is not None:
+            raise RuntimeError("attach_records must precede capture(): the ring's address is baked into the graph")
+        cap = max(int(capacity_frames), self.B)
+        f32, i32 = torch.float32, torch.int32
+        self.records = torch.zeros((cap, self.post_max, 9), dtype=f32, device=self.dev)
+        self.record_counts = torch.zeros((cap,), dtype=i32, device=self.dev)
+        self.record_cursor = torch.zeros((1,), dtype=i32, device=self.dev)
+        return self.records, self.record_counts
+
+    def _wgs(self):
+        """persistent workgroups of a stream-K launch of ops.conv2d (InferenceEngine._wgs): 0 = the library's choice for the whole chip"""
+        return max(8, int(self.cu_budget) & ~7) if self.cu_budget else 0
 
     def _default_anchors(self, head):
         from . import configs
@@ -252,49 +294,74 @@ class PillarEngine:
     def enqueue(self):
         """One batch on the current stream: no host synchronisation, every count on the device, every buffer static."""
         s = torch.cuda.current_stream().cuda_stream
+        self._enqueue_front(s)
+        return self._enqueue_rest(s)
+
+    def _enqueue_front(self, s):
+        """staged clouds -> canvas (scripts/pillar_front_end_probe.py times this part alone)"""
         B = self.B
-        # ---- 1. voxelize: hash clear + the four launches of all frames (the per-cell lists are cleared inside)
-        self.hash.clear()
-        check(lib.sessd_voxelize_frames(self.points.data_ptr(), B, self.P_cap, 4, self.vrange.data_ptr(), self.vsize.data_ptr(),
-                                        self.grid.data_ptr(), self.T, self.max_voxels, self.hash.keys.data_ptr(),
-                                        self.hash.vals.data_ptr(), self.hash.capacity, self.voxels.data_ptr(), self.coors.data_ptr(), 4,
-                                        self.nump.data_ptr(), self.mean.data_ptr(), self.prefix.data_ptr(), self.vox_ws.data_ptr(),
-                                        self.vox_ws.numel(), s), "voxelize_frames")
-        self._mark("voxelize")
-        # ---- 2. canvas clear, then pillar features with the canvas written in the SAME launch (no feature rows kept)
-        check(lib.sessd_fill_u32(self.canvas.data_ptr(), 0, self.canvas.numel(), s), "fill_u32")
-        self._mark("canvas_clear")
         vx, vy, xo, yo = self.reader_geom
-        check(lib.sessd_pillar_features(self.voxels.data_ptr(), self.nump.data_ptr(), self.coors.data_ptr(),
-                                        self.prefix[B:].data_ptr(), self.cap, self.T, 4, vx, vy, xo, yo, self.pfn_w.data_ptr(),
-                                        self.pfn_scale.data_ptr(), self.pfn_shift.data_ptr(), ops.PILLAR_CHANNELS,
-                                        1 if self.with_distance else 0, B, self.ny, self.nx, 0, self.canvas.data_ptr(),
-                                        self.err.data_ptr(), s), "pillar_features")
-        self._mark("pillar")
+        self.hash.clear()
+        if self.front_end == "fused":
+            # ---- 1 / 2. hash clear, canvas clear, then clouds -> canvas in five launches (no pillar tensor, no feature rows)
+            check(lib.sessd_fill_u32(self.canvas.data_ptr(), 0, self.canvas.numel(), s), "fill_u32")
+            self._mark("canvas_clear")
+            check(lib.sessd_pillar_frames(self.points.data_ptr(), B, self.P_cap, 4, self.vrange.data_ptr(), self.vsize.data_ptr(),
+                                          self.grid.data_ptr(), self.T, self.max_voxels, self.hash.keys.data_ptr(),
+                                          self.hash.vals.data_ptr(), self.hash.capacity, vx, vy, xo, yo, self.pfn_w.data_ptr(),
+                                          self.pfn_scale.data_ptr(), self.pfn_shift.data_ptr(), ops.PILLAR_CHANNELS,
+                                          1 if self.with_distance else 0, self.ny, self.nx, self.canvas.data_ptr(),
+                                          self.coors.data_ptr(), self.prefix.data_ptr(), self.nump.data_ptr(), 0, self.err.data_ptr(),
+                                          self.vox_ws.data_ptr(), self.vox_ws.numel(), s), "pillar_frames")
+            self._mark("front_end")
+        else:
+            # ---- 1. voxelize: hash clear + the four launches of all frames (the per-cell lists are cleared inside)
+            check(lib.sessd_voxelize_frames(self.points.data_ptr(), B, self.P_cap, 4, self.vrange.data_ptr(), self.vsize.data_ptr(),
+                                            self.grid.data_ptr(), self.T, self.max_voxels, self.hash.keys.data_ptr(),
+                                            self.hash.vals.data_ptr(), self.hash.capacity, self.voxels.data_ptr(), self.coors.data_ptr(), 4,
+                                            self.nump.data_ptr(), self.mean.data_ptr(), self.prefix.data_ptr(), self.vox_ws.data_ptr(),
+                                            self.vox_ws.numel(), s), "voxelize_frames")
+            self._mark("voxelize")
+            # ---- 2. canvas clear, then pillar features with the canvas written in the SAME launch (no feature rows kept)
+            check(lib.sessd_fill_u32(self.canvas.data_ptr(), 0, self.canvas.numel(), s), "fill_u32")
+            self._mark("canvas_clear")
+            check(lib.sessd_pillar_features(self.voxels.data_ptr(), self.nump.data_ptr(), self.coors.data_ptr(),
+                                            self.prefix[B:].data_ptr(), self.cap, self.T, 4, vx, vy, xo, yo, self.pfn_w.data_ptr(),
+                                            self.pfn_scale.data_ptr(), self.pfn_shift.data_ptr(), ops.PILLAR_CHANNELS,
+                                            1 if self.with_distance else 0, B, self.ny, self.nx, 0, self.canvas.data_ptr(),
+                                            self.err.data_ptr(), s), "pillar_features")
+            self._mark("pillar")
+
+    def _enqueue_rest(self, s):
+        B = self.B
         # ---- 3 / 4. the RPN blocks, each followed by its up-sampler into its channels of the neck map
         x = self.canvas
+        wgs = self._wgs()
         for i, (blk, u) in enumerate(zip(self.blocks, self.ups)):
             for L in blk:
-                x = ops.conv2d(x, L["pc"], L["scale"], L["shift"], True, None, out=L["out"])
+                x = ops.conv2d(x, L["pc"], L["scale"], L["shift"], True, None, out=L["out"], workgroups=wgs)
             self._mark("blk%d" % i)
             if self._fused(i):
                 ops.deconv_ks_slice(x, u["fused"], u["scale"], u["shift"], True, self.neck, u["c_off"])
             else:
-                ops.conv2d(x, u["parent"], u["scale"], u["shift"], True, None, out=u["scratch"])
+                ops.conv2d(x, u["parent"], u["scale"], u["shift"], True, None, out=u["scratch"], workgroups=wgs)
                 self.neck[:, u["c_off"]:u["c_off"] + u["cout"]].copy_(u["scratch"])
             self._mark("up%d" % i)
         # ---- 5. head
-        ops.conv2d(self.neck, self.head_pc, None, self.head_b, False, None, out=self.head.view(B, ops.TASK_HEAD_CH, self.H, self.W))
+        ops.conv2d(self.neck, self.head_pc, None, self.head_b, False, None, out=self.head.view(B, ops.TASK_HEAD_CH, self.H, self.W),
+                   workgroups=wgs)
         self._mark("head")
         # ---- 6. predict
         ops.predict(self.head, self.anchors, None, self.score_thresh, self.pre_max, self.post_max, self.nms_thresh, self.post_range,
-                    self.dir_offset, out=self.out, nms_type=self.nms_type, di=self.di)
+                    self.dir_offset, out=self._pred_out, nms_type=self.nms_type, di=self.di,
+                    records=None if self.records is None else (self.records, self.record_counts, self.record_cursor))
         self._mark("predict")
         return self.out
 
     def stage_times(self, reps=10):
         """Eager per-stage device time in ms of the staged batch (HIP events on the current stream, launch gaps of eager mode
-        included): voxelize (with its hash and list clears), canvas_clear, pillar, blk<i>, up<i>, head, predict."""
+        included): voxelize (with its hash and list clears), canvas_clear, pillar -- front_end "fused": canvas_clear (with the hash
+        clear), front_end (the five launches of sessd_pillar_frames) -- then blk<i>, up<i>, head, predict."""
         acc = {}
         for _ in range(2):
             self.enqueue()
@@ -337,7 +404,7 @@ class PillarEngine:
         cnt = self.out["count"].cpu().numpy()
         if int(self.err.item()) != 0:
             self.err.zero_()
-            raise RuntimeError("a pillar's cell lies outside the %d x %d canvas: voxel range and canvas do not match" % (self.ny, self.nx))
+            raise RuntimeError(self.err_text)
         res = []
         for b in range(self.B):
             n = int(cnt[b])

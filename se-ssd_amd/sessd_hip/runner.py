@@ -77,6 +77,34 @@ def engines_on_cu_sets(model, voxel_range, voxel_size, max_points_per_voxel, max
     return engines, streams
 
 
+def pillar_engines_on_cu_sets(model, voxel_generator_cfg, test_cfg, n_engines=4, sets=2, device=None, layout="contiguous", capture=True,
+                              records=0, **engine_kwargs):
+    """engines_on_cu_sets for the PointPillars config: `n_engines` batch-1 PillarEngines, engine i on a stream of its own that is
+    confined to CU set i % `sets` (ops.cu_masked_stream), cu_budget set to the set's size. There is nothing to tune (the engine has
+    no tile lists and no autotuned layers). records > 0: a device detection ring of that many frames is attached first
+    (HostFedPipeline attaches its own to engines that are not captured yet); capture: every engine's graph is captured on its
+    stream. engine_kwargs go to PillarEngine (max_points, anchors, front_end). Returns (engines, streams); HostFedPipeline takes
+    them as they are. `sets` must divide the chip's 8 XCDs evenly (2 or 4)."""
+    from . import ops
+    from .pillar_engine import PillarEngine
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    engines, streams = [], []
+    for k in range(int(n_engines)):
+        st, ncu = ops.cu_masked_stream(k % int(sets), int(sets), dev, layout=layout)
+        e = PillarEngine(model, voxel_generator_cfg, test_cfg, 1, device=dev, **engine_kwargs)
+        e.cu_budget = ncu
+        engines.append(e)
+        streams.append(st)
+    for e, st in zip(engines, streams):
+        if records:
+            e.attach_records(int(records))
+        if capture:
+            with torch.cuda.stream(st):
+                e.capture()
+    torch.cuda.synchronize(dev)
+    return engines, streams
+
+
 class HostFedPipeline:
     def __init__(self, engines, streams=None, ring=4, fetch_every=16, eager=False, copy_mode="instream"):
         """engines: batch-1 InferenceEngines of ONE configuration (captured unless eager=True). ring: staging buffers per
@@ -226,8 +254,9 @@ class HostFedPipeline:
             # a sparse level overflowed in one of the frames up to this fetch: their rows were dropped, the detections are not
             # to be handed out. The flag is sticky on the device; clear it so that a new job can start after reset().
             self.engines[ei].err.zero_()
-            raise RuntimeError("sparse level capacity overflow in a frame of engine %d up to its frame %d (job frames <= %d): "
-                               "raise `growth` or max_voxels" % (ei, lo + cnt - 1, self._base + (lo + cnt - 1) * len(self.engines) + ei))
+            raise RuntimeError(getattr(self.engines[ei], "err_text",
+                                       "sparse level capacity overflow in a frame of engine %d up to its frame %d (job frames <= %d): "
+                                       "raise `growth` or max_voxels" % (ei, lo + cnt - 1, self._base + (lo + cnt - 1) * len(self.engines) + ei)))
         rec, c = st["host_rec"][buf].numpy(), st["host_cnt"][buf].numpy()
         E = len(self.engines)
         for j in range(cnt):
@@ -259,7 +288,7 @@ class HostFedPipeline:
         for e in self.engines:
             if int(e.err.item()) != 0:  # (every fetch carries the flag; this is the belt to those braces)
                 e.err.zero_()
-                raise RuntimeError("sparse level capacity overflow: raise `growth` or max_voxels")
+                raise RuntimeError(getattr(e, "err_text", "sparse level capacity overflow: raise `growth` or max_voxels"))
         # DI-NMS engines (test_cfg nms_type "rotate_weighted_nms"): did any frame of the job stop its selection at post_max with
         # candidates left? Reported, never raised (the detections are the reference's keep list cut at post_max)
         self.nms_truncated = any(int(e.nms_truncated.item()) != 0 for e in self.engines)

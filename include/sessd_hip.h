@@ -131,6 +131,72 @@ int sessd_pillar_frames(const float* points, int batch, int points_per_frame, in
                         float y_offset, const float* weight, const float* scale, const float* shift, int channels,
                         int with_distance, int ny, int nx, float* canvas, int32_t* coors, int32_t* prefix, int32_t* num_points,
                         float* feat, int32_t* err_flag, void* workspace, size_t workspace_bytes, sessd_stream_t stream);
+/* PillarFeatureNet with ONE PFNLayer in TRAIN mode and the scatter's gradient (csrc/pillar.hip): replaces Linear +
+ * BatchNorm1d(training) + ReLU + max over the slots (det3d/models/readers/pillar_encoder.py:42-57, 114-153) and their autograd
+ * graph, without the (N, T, K) tensors. voxels, num_points, coors, num_voxels_dev / num_voxels_host (>= 1), T, ndim, vx .. y_offset,
+ * weight (channels, num_columns): as sessd_pillar_features; channels = 64, num_columns = 9 (with_distance: 10).
+ *
+ * BatchNorm1d normalises a channel over all M = n * T slots, the padding slots (Linear output 0) included. With f_i the decorated
+ * row of live slot i -- sessd_pillar_features' columns, formed in float64 from the float32 points, so that the statistics and the
+ * gradients carry no float32 rounding of the means; the SELECTION alone runs the forward's float32 arithmetic --
+ * S1 = sum f_i and G = sum f_i f_i^T over the live slots of the first n pillars:
+ *   sum z_c = w_c . S1,  sum z_c^2 = w_c^T G w_c,  mean = sum z / M,  var = sum z^2 / M - mean^2,  invstd = 1 / sqrt(var + eps)
+ *   scale = gamma * invstd,  shift = beta - mean * scale,  and the train-mode output IS sessd_pillar_features(scale, shift).
+ * Backward, upstream gradient g (N_cap, 64): per (pillar, channel) the selected slot s is the FIRST slot whose value equals the
+ * stored output bit for bit, found by running the forward's arithmetic again (the same device function); the padding candidate
+ * relu(shift) stands behind every live slot, so a live slot wins an exact tie. dy = g where the selected value is > 0, else 0;
+ * xhat = (z_s - mean) * invstd for a live slot, -mean * invstd for a padding slot;
+ *   dbeta = sum dy,  dgamma = sum dy * xhat,  P_c = sum over live selected slots of dy * f_s,
+ *   dW_c = scale_c * [P_c - dbeta_c / M * S1 - dgamma_c / M * invstd_c * (G w_c - mean_c * S1)].
+ * The points carry no gradient.
+ *
+ * Layouts (float64): totals = [S1 (K), G's upper triangle by rows (K (K + 1) / 2), M]: sessd_pillar_train_totals() numbers;
+ * bwd_totals = [sum dy (64), sum dy * z_s (64; z_s = w . f_s, 0 for a padding slot), P (64, K)]: sessd_pillar_train_bwd_totals()
+ * numbers, every one additive over the ranks; dgamma = invstd * (sum dy z_s - mean * sum dy). All totals are accumulated in float64
+ * in a fixed order (per-block partials; the last block of a group of 16 to arrive adds the group's in block order, the last group
+ * adds the groups' in group order): two calls give the same bits. No floating-point atomics. workspace:
+ * sessd_pillar_train_workspace_bytes(); its first 256 bytes are the arrival counters, ZERO on entry and zero again on return (as
+ * sessd_bn_relu_train_fwd's).
+ *
+ *   sessd_pillar_train_stats        one wave per pillar, only live slots read -> totals (this rank's)
+ *   sessd_pillar_train_finalize     totals (summed over the ranks under SyncBN: every entry is additive) -> mean, invstd, scale,
+ *                                   shift (float32, 64 each); running_mean / running_var (both or neither) updated in place:
+ *                                   running = (1 - momentum) * running + momentum * batch, variance unbiased (M / (M - 1)); M = 1
+ *                                   takes the biased variance, M = 0 gives mean 0, var 0 and leaves them alone -- exactly
+ *                                   sessd_bn_relu_train_apply's rule for its row count
+ *   [sessd_pillar_features]         the forward output with (scale, shift)
+ *   sessd_pillar_train_bwd_select   scale / shift = the forward's, feat = the forward output, grad_feat = g -> bwd_totals (this rank's)
+ *   sessd_pillar_train_bwd_finalize -> grad_weight (64, K), grad_gamma, grad_beta (float32); mean, invstd and scale are formed again
+ *                                   in float64 from totals_all, weight, gamma, eps. bwd_totals / totals: this rank's (P, S1, G;
+ *                                   grad_gamma and grad_beta are this rank's sums); bwd_totals_all / totals_all: summed over the
+ *                                   ranks (dbeta, dgamma and M inside the dW formula). One rank: pass the same pointers twice.
+ *   sessd_pillar_scatter_bwd        grad_feat[p][c] = grad_canvas[b][c][y][x], one wave per row of grad_feat (num_voxels_host, 64):
+ *                                   a pillar whose cell lies outside (batch, ny, nx) gets a zero row and reads nothing; rows >= n
+ *                                   are zero (their coors are not read).
+ * SESSD_EINVAL before any device call: ndim != 4, channels != 64, num_columns != 9 + with_distance, T < 1, num_voxels_host < 1, a
+ * NULL pointer (num_voxels_dev may be NULL; running_mean and running_var may both be NULL), only one of the running statistics,
+ * workspace_bytes below sessd_pillar_train_workspace_bytes(); sessd_pillar_scatter_bwd: channels != 64, batch, ny or nx < 1. */
+size_t sessd_pillar_train_totals(int with_distance);
+size_t sessd_pillar_train_bwd_totals(int with_distance);
+size_t sessd_pillar_train_workspace_bytes(int with_distance);
+int sessd_pillar_train_stats(const float* voxels, const int32_t* num_points, const int32_t* coors, const int32_t* num_voxels_dev,
+                             int num_voxels_host, int max_points_per_voxel, int ndim, float vx, float vy, float x_offset,
+                             float y_offset, int channels, int num_columns, int with_distance, double* totals, void* workspace,
+                             size_t workspace_bytes, sessd_stream_t stream);
+int sessd_pillar_train_finalize(const double* totals, const float* weight, const float* gamma, const float* beta, float eps,
+                                float momentum, int channels, int num_columns, int with_distance, float* running_mean,
+                                float* running_var, float* mean, float* invstd, float* scale, float* shift, sessd_stream_t stream);
+int sessd_pillar_train_bwd_select(const float* voxels, const int32_t* num_points, const int32_t* coors, const int32_t* num_voxels_dev,
+                                  int num_voxels_host, int max_points_per_voxel, int ndim, float vx, float vy, float x_offset,
+                                  float y_offset, const float* weight, const float* scale, const float* shift, int channels,
+                                  int num_columns, int with_distance, const float* feat, const float* grad_feat, double* bwd_totals,
+                                  void* workspace, size_t workspace_bytes, sessd_stream_t stream);
+int sessd_pillar_train_bwd_finalize(const double* bwd_totals, const double* bwd_totals_all, const double* totals,
+                                    const double* totals_all, const float* weight, const float* gamma, float eps, int channels,
+                                    int num_columns, int with_distance, float* grad_weight, float* grad_gamma, float* grad_beta,
+                                    sessd_stream_t stream);
+int sessd_pillar_scatter_bwd(const float* grad_canvas, const int32_t* coors, const int32_t* num_voxels_dev, int num_voxels_host,
+                             int channels, int batch, int ny, int nx, float* grad_feat, sessd_stream_t stream);
 /* An up-sampler of the RPN neck straight into its channels of the concatenated map (csrc/deconv_ks.hip): replaces
  * nn.ConvTranspose2d(cin, cout, s, stride=s, bias=False) + BatchNorm2d + ReLU (det3d/models/necks/rpn_v1.py:84-105) and the
  * torch.cat of the up-samplers' outputs (:116), in ONE launch on the exact-f32 matrix cores:

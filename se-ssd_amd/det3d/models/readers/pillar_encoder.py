@@ -2,7 +2,9 @@
 (:156-208). Same constructor arguments, defaults and state_dict keys (`pfn_layers.0.linear.weight`, `pfn_layers.0.norm.*`).
 
 Device path: ONE PFN layer in eval mode on a device tensor runs ops.pillar_features (sessd_pillar_features), the scatter runs
-ops.pillar_scatter. More than one layer, training mode, a tensor that carries a gradient or a CPU tensor run the torch
+ops.pillar_scatter. In train mode the same layer runs ops.pillar_features_train (batch statistics from float64 totals over the
+live points, the eval kernel with them, a backward by recomputation: `fused_train`), and a scatter whose features carry a gradient
+runs ops.pillar_scatter_train. More than one layer, a point tensor that carries a gradient or a CPU tensor run the torch
 formulation below (`_forward_torch`), written for this project: the padding slots are masked before anything is computed from
 them, the per-pillar constants are broadcast, BatchNorm is one functional call over the flattened slots, the scatter is one
 indexed store. tests/test_pillars_mirror_cpu.py holds it to the reference's classes run from source.
@@ -46,6 +48,8 @@ class PFNLayer(nn.Module):
 
 @READERS.register_module
 class PillarFeatureNet(nn.Module):
+    fused_train = True   # train mode on the device: ops.pillar_features_train (False: the torch formulation), cf. RPN.fused_bn_train
+
     def __init__(self, num_input_features=4, num_filters=(64,), with_distance=False, voxel_size=(0.2, 0.2, 4),
                  pc_range=(0, -40, -3, 70.4, 40, 1), norm_cfg=None):
         super().__init__()
@@ -66,12 +70,25 @@ class PillarFeatureNet(nn.Module):
         return (len(self.pfn_layers) == 1 and not self.training and features.is_cuda and not features.requires_grad
                 and features.shape[-1] == 4 and pfn.units == ops.PILLAR_CHANNELS and isinstance(pfn.norm, nn.BatchNorm1d))
 
+    def on_device_train_path(self, features):
+        """The same layer in train mode: what ops.pillar_features_train covers (a plain BatchNorm1d whose batch holds at least two
+        slots; the points carry no gradient)."""
+        pfn = self.pfn_layers[0]
+        return (self.fused_train and len(self.pfn_layers) == 1 and self.training and features.is_cuda
+                and not features.requires_grad and features.dim() == 3 and features.shape[-1] == 4
+                and pfn.units == ops.PILLAR_CHANNELS and type(pfn.norm) is nn.BatchNorm1d
+                and features.shape[0] * features.shape[1] >= 2)
+
     def forward(self, features, num_voxels, coors):
         """features (N, T, 4), num_voxels (N,) points per pillar, coors (N, 4) [b, z, y, x] -> (N, C). The reference's trailing
         `.squeeze()` collapses N = 1 to (C,); this returns (N, C) always."""
+        pfn = self.pfn_layers[0]
+        if self.on_device_train_path(features):
+            return ops.pillar_features_train(features.float().contiguous(), num_voxels.int().contiguous(), coors.int().contiguous(),
+                                             pfn.linear.weight, pfn.norm, self.vx, self.vy, self.x_offset, self.y_offset,
+                                             with_distance=self._with_distance)
         if not self.on_device_path(features):
             return self._forward_torch(features, num_voxels, coors)
-        pfn = self.pfn_layers[0]
         scale, shift = fold_bn(pfn.norm)
         return ops.pillar_features(features.float().contiguous(), num_voxels.int().contiguous(), coors.int().contiguous(),
                                    pfn.linear.weight.detach().float().contiguous(), scale, shift, self.vx, self.vy,
@@ -106,6 +123,9 @@ class PointPillarsScatter(nn.Module):
     def forward(self, voxel_features, coords, batch_size, input_shape):
         """voxel_features (N, C), coords (N, 4) [b, z, y, x], input_shape [nx, ny, ...] -> (batch_size, C, ny, nx)."""
         self.nx, self.ny = int(input_shape[0]), int(input_shape[1])
+        if voxel_features.is_cuda and voxel_features.shape[1] == ops.PILLAR_CHANNELS and voxel_features.requires_grad:
+            return ops.pillar_scatter_train(voxel_features.float().contiguous(), coords.int().contiguous(), int(batch_size), self.ny,
+                                            self.nx)
         if (voxel_features.is_cuda and voxel_features.shape[1] == ops.PILLAR_CHANNELS and not self.training
                 and not voxel_features.requires_grad):
             return ops.pillar_scatter(voxel_features.float().contiguous(), coords.int().contiguous(), int(batch_size), self.ny,

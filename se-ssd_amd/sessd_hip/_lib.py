@@ -87,6 +87,15 @@ SIGNATURES = {
     "sessd_pillar_frames_workspace_bytes": (sz, [u32, i32, i32, i32, i32]),
     "sessd_pillar_frames": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, u32, f32, f32, f32, f32, vp, vp, vp, i32, i32, i32, i32,
                                   vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "sessd_pillar_train_totals": (sz, [i32]),
+    "sessd_pillar_train_bwd_totals": (sz, [i32]),
+    "sessd_pillar_train_workspace_bytes": (sz, [i32]),
+    "sessd_pillar_train_stats": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, i32, i32, i32, vp, vp, sz, vp]),
+    "sessd_pillar_train_finalize": (i32, [vp, vp, vp, vp, f32, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "sessd_pillar_train_bwd_select": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp,
+                                            sz, vp]),
+    "sessd_pillar_train_bwd_finalize": (i32, [vp, vp, vp, vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, vp]),
+    "sessd_pillar_scatter_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     "sessd_deconv_ks_slice":(i32, [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp]),
     "sessd_boxes_pairwise": (i32, [i32, vp, i32, vp, i32, vp, vp]),
     "sessd_boxes_aligned_overlap_bev": (i32, [vp, vp, i32, vp, vp]),

@@ -385,6 +385,138 @@ def pillar_scatter(feat, coors, batch, ny, nx, num_voxels_dev=None, err_flag=Non
     return canvas
 
 
+class PillarFeaturesTrainFunction(torch.autograd.Function):
+    """One PFN layer in train mode (csrc/pillar.hip): statistics over the live points -> [all-reduce under SyncBN] -> mean, invstd,
+    scale, shift -> the eval kernel with them; backward by recomputation of the selected slot. Saves the inputs, the float64 totals,
+    mean, invstd, scale, shift and the (N, 64) output: nothing of size N * T * 64."""
+
+    @staticmethod
+    def forward(ctx, weight, gamma, beta, voxels, num_points, coors, running_mean, running_var, eps, momentum, geom, with_distance,
+                num_voxels_dev):
+        dev = voxels.device
+        N, T, ndim = voxels.shape
+        C, K = weight.shape
+        dist = 1 if with_distance else 0
+        w = weight.detach().float().contiguous()
+        g, b = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+        vx, vy, xo, yo = geom
+        totals = torch.empty(int(lib.sessd_pillar_train_totals(dist)), dtype=torch.float64, device=dev)
+        ws = zeroed_workspace(lib.sessd_pillar_train_workspace_bytes(dist), dev, "pillar_train")
+        check(lib.sessd_pillar_train_stats(voxels.data_ptr(), num_points.data_ptr(), coors.data_ptr(), _p(num_voxels_dev), N, T, ndim,
+                                           vx, vy, xo, yo, C, K, dist, totals.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+              "pillar_train_stats")
+        sync = sync_bn_active()
+        totals_all = totals
+        if sync:   # S1, G and M are additive over the ranks; this rank's own copy stays for the backward's dW
+            totals_all = totals.clone()
+            _sync_reduce(totals_all)
+        mean, invstd, scale, shift = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(4))
+        check(lib.sessd_pillar_train_finalize(totals_all.data_ptr(), w.data_ptr(), g.data_ptr(), b.data_ptr(), float(eps),
+                                              float(momentum), C, K, dist, _p(running_mean), _p(running_var), mean.data_ptr(),
+                                              invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), _stream()), "pillar_train_finalize")
+        feat = fill_zero(torch.empty((N, C), dtype=torch.float32, device=dev))   # rows >= *num_voxels_dev stay zero
+        check(lib.sessd_pillar_features(voxels.data_ptr(), num_points.data_ptr(), coors.data_ptr(), _p(num_voxels_dev), N, T, ndim,
+                                        vx, vy, xo, yo, w.data_ptr(), scale.data_ptr(), shift.data_ptr(), C, dist, 0, 0, 0,
+                                        feat.data_ptr(), 0, 0, _stream()), "pillar_features")
+        saved = [voxels, num_points, coors, w, g, totals, totals_all, mean, invstd, scale, shift, feat]
+        if num_voxels_dev is not None:
+            saved.append(num_voxels_dev)
+        ctx.save_for_backward(*saved)
+        ctx.geom, ctx.dist, ctx.sync, ctx.eps = geom, dist, sync, float(eps)
+        return feat
+
+    @staticmethod
+    def backward(ctx, grad):
+        voxels, num_points, coors, w, gamma, totals, totals_all, _mean, _invstd, scale, shift, feat = ctx.saved_tensors[:12]
+        n_dev = ctx.saved_tensors[12] if len(ctx.saved_tensors) > 12 else None
+        dev = voxels.device
+        N, T, ndim = voxels.shape
+        C, K = w.shape
+        vx, vy, xo, yo = ctx.geom
+        grad = grad.float().contiguous()
+        bwd = torch.empty(int(lib.sessd_pillar_train_bwd_totals(ctx.dist)), dtype=torch.float64, device=dev)
+        ws = zeroed_workspace(lib.sessd_pillar_train_workspace_bytes(ctx.dist), dev, "pillar_train")
+        check(lib.sessd_pillar_train_bwd_select(voxels.data_ptr(), num_points.data_ptr(), coors.data_ptr(), _p(n_dev), N, T, ndim, vx, vy,
+                                                xo, yo, w.data_ptr(), scale.data_ptr(), shift.data_ptr(), C, K, ctx.dist,
+                                                feat.data_ptr(), grad.data_ptr(), bwd.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                _stream()), "pillar_train_bwd_select")
+        bwd_all = bwd
+        if ctx.sync:   # the sums of dy and dy * z of all ranks go into dW; P stays this rank's
+            bwd_all = bwd[:2 * C].clone()
+            _sync_reduce(bwd_all)
+        dw = torch.empty((C, K), dtype=torch.float32, device=dev)
+        dg, db = torch.empty(C, dtype=torch.float32, device=dev), torch.empty(C, dtype=torch.float32, device=dev)
+        check(lib.sessd_pillar_train_bwd_finalize(bwd.data_ptr(), bwd_all.data_ptr(), totals.data_ptr(), totals_all.data_ptr(),
+                                                  w.data_ptr(), gamma.data_ptr(), ctx.eps, C, K, ctx.dist, dw.data_ptr(), dg.data_ptr(),
+                                                  db.data_ptr(), _stream()), "pillar_train_bwd_finalize")
+        return (dw, dg, db) + (None,) * 10
+
+
+def pillar_features_train(voxels, num_points, coors, linear_weight, bn, vx, vy, x_offset, y_offset, with_distance=False,
+                          num_voxels_dev=None):
+    """PillarFeatureNet with one PFNLayer in TRAIN mode: voxels (N, T, 4), num_points (N) int32, coors (N, 4) int32, linear_weight
+    (64, 9 | 10), bn the layer's nn.BatchNorm1d (batch statistics over all N * T slots; its running statistics are updated in place
+    and the batch is counted) -> (N, 64) features that carry a graph to linear_weight, bn.weight and bn.bias. The points carry no
+    gradient. num_voxels_dev: device int32 live count; feature rows beyond it are zero. Under set_sync_bn the float64 totals pass
+    through ONE all-reduce in each direction."""
+    _req(voxels, torch.float32, "voxels")
+    _req(num_points, torch.int32, "num_points")
+    _req(coors, torch.int32, "coors")
+    for t, name in ((linear_weight, "linear_weight"), (bn.weight, "bn.weight"), (bn.bias, "bn.bias")):
+        if t is None or not t.is_cuda:
+            raise ValueError("%s must be a CUDA (HIP) tensor: the SE-SSD hot path has no CPU fallback" % name)
+    if voxels.dim() != 3 or voxels.shape[2] != 4 or voxels.shape[0] < 1 or voxels.shape[1] < 1:
+        raise ValueError("pillar_features_train: voxels (N >= 1, T >= 1, 4) expected")
+    N = voxels.shape[0]
+    K = 10 if with_distance else 9
+    C = PILLAR_CHANNELS
+    if tuple(linear_weight.shape) != (C, K) or bn.weight.numel() != C or bn.bias.numel() != C:
+        raise ValueError("pillar_features_train: linear_weight (%d, %d) and a BatchNorm1d(%d) expected" % (C, K, C))
+    if num_points.numel() != N or tuple(coors.shape) != (N, 4):
+        raise ValueError("pillar_features_train: num_points (N), coors (N, 4) expected")
+    if num_voxels_dev is not None:
+        _req(num_voxels_dev, torch.int32, "num_voxels_dev")
+    mom = _bn_momentum(bn)
+    geom = (float(vx), float(vy), float(x_offset), float(y_offset))
+    return PillarFeaturesTrainFunction.apply(linear_weight, bn.weight, bn.bias, voxels, num_points, coors, bn.running_mean,
+                                             bn.running_var, bn.eps, mom, geom, bool(with_distance), num_voxels_dev)
+
+
+class PillarScatterTrainFunction(torch.autograd.Function):
+    """pillar_scatter with its gradient: grad_feat[p] = the canvas gradient's column at pillar p's cell (sessd_pillar_scatter_bwd)."""
+
+    @staticmethod
+    def forward(ctx, feat, coors, batch, ny, nx, num_voxels_dev):
+        ctx.save_for_backward(*([coors] if num_voxels_dev is None else [coors, num_voxels_dev]))
+        ctx.shape = (int(batch), int(ny), int(nx))
+        return pillar_scatter(feat, coors, batch, ny, nx, num_voxels_dev=num_voxels_dev)
+
+    @staticmethod
+    def backward(ctx, grad):
+        coors = ctx.saved_tensors[0]
+        n_dev = ctx.saved_tensors[1] if len(ctx.saved_tensors) > 1 else None
+        batch, ny, nx = ctx.shape
+        N, C = coors.shape[0], PILLAR_CHANNELS
+        grad = grad.float().contiguous()
+        out = torch.empty((N, C), dtype=torch.float32, device=grad.device)
+        if N > 0:
+            check(lib.sessd_pillar_scatter_bwd(grad.data_ptr(), coors.data_ptr(), _p(n_dev), N, C, batch, ny, nx, out.data_ptr(), _stream()),
+                  "pillar_scatter_bwd")
+        return out, None, None, None, None, None
+
+
+def pillar_scatter_train(feat, coors, batch, ny, nx, num_voxels_dev=None):
+    """ops.pillar_scatter that keeps the graph: feat (N, 64) -> (batch, 64, ny, nx); the backward gathers the canvas gradient's
+    columns (zero rows for pillars outside the canvas and for rows beyond *num_voxels_dev)."""
+    _req(feat, torch.float32, "feat")
+    _req(coors, torch.int32, "coors")
+    if feat.dim() != 2 or feat.shape[1] != PILLAR_CHANNELS or tuple(coors.shape) != (feat.shape[0], 4):
+        raise ValueError("pillar_scatter_train: feat (N, %d), coors (N, 4) expected" % PILLAR_CHANNELS)
+    if num_voxels_dev is not None:
+        _req(num_voxels_dev, torch.int32, "num_voxels_dev")
+    return PillarScatterTrainFunction.apply(feat, coors, int(batch), int(ny), int(nx), num_voxels_dev)
+
+
 # ------------------------------------------------------------------ iou3d operators
 def boxes_pairwise(mode, a, b, out=None):
     w = 7 if mode in (2, 3) else 5

@@ -737,6 +737,18 @@ int sessd_deconv2d_s2_mfma_pair_active(const float* in, int batch, int cin, int 
                                        const float* scale_b, const float* shift_b, int relu, const float* residual_a,
                                        const float* residual_b, const int32_t* tile_list, const int32_t* n_list, int list_cap,
                                        int tile_cfg, sessd_stream_t stream);
+/* sessd_deconv2d_s2_mfma_pair_active on the bf16 matrix cores at f32 accuracy (csrc/dense_deconv_split.hip): every operand split
+ * into three bf16 terms, six products per operand pair, f32 accumulation; the same contract (listed 2x2 input tiles -> 4x4 blocks
+ * of both outputs, nothing else touched). wsplit_a / wsplit_b: each layer's (cin, cout, 3, 3) weight as three bf16 planes in the
+ * kernel's fragment order, [ceil(cout / 128)][cin / 16][tap 9][plane 3][cout block 4][lane 64][8] (ops.pack_deconv2d_s2(w).wsplit());
+ * the tap tables are the fixed ones of a stride-2 3x3 transposed conv. cin % 16 == 0, even hin / win, the whole batch inside
+ * 32-bit buffer offsets; anything else returns SESSD_EINVAL. One workgroup per (16 list entries, 128 couts, layer), sized from
+ * list_cap; a listed block's bits do not depend on the rest of the list. */
+int sessd_deconv2d_s2_pair_split_active(const float* in, int batch, int cin, int hin, int win, const void* wsplit_a,
+                                        const void* wsplit_b, float* out_a, float* out_b, int cout, const float* scale_a,
+                                        const float* shift_a, const float* scale_b, const float* shift_b, int relu,
+                                        const float* residual_a, const float* residual_b, const int32_t* tile_list,
+                                        const int32_t* n_list, int list_cap, sessd_stream_t stream);
 /* rpn_v1.py:227-233: softmax over the two 1-channel weight maps and the weighted sum of x0, x1 */
 int sessd_ssfa_fuse(const float* x0, const float* x1, const float* w0, const float* w1, float bn_scale0,
                     float bn_shift0, float bn_scale1, float bn_shift1, int batch, int channels, int num_pixels,

@@ -797,11 +797,19 @@ int launch_conv(const ConvArgs* A, int nconv, int batch, hipStream_t stream) {
   return SESSD_OK;
 }
 
+// Pixel slots of a LIST launch: the whole map, and never fewer than the list can hold -- 32 entries take 128 slots (list_pixel),
+// so a map whose tile count is no multiple of 32 (or smaller than one unit) needs more slots than it has pixels.
+inline int list_launch_pixels(const ConvArgs& A, int npix, int batch) {
+  const int need = sessd_divup(A.list_cap, 32) * 128;
+  return npix * batch > need ? npix * batch : need;
+}
+
 template <int CT, int PT, int WC, int WP, bool DEEP>
 int launch_conv8(const ConvArgs* A, int batch, hipStream_t stream) {
   const int npix = A[0].ht * A[0].wt;
   const bool list = A[0].tile_list != nullptr;   // the images of a list launch share the pixel axis
-  dim3 grid(sessd_divup(npix * (list ? batch : 1), WP * PT * 32) * sessd_divup(A[0].cout_pad, WC * CT * 32), 1, (list ? 1 : batch) * 8);
+  dim3 grid(sessd_divup(list ? list_launch_pixels(A[0], npix, batch) : npix, WP * PT * 32) * sessd_divup(A[0].cout_pad, WC * CT * 32), 1,
+            (list ? 1 : batch) * 8);
   ConvArgs8 A8;
   for (int i = 0; i < 8; ++i) A8.c[i] = A[i];
   if (list)
@@ -816,7 +824,7 @@ int launch_conv8(const ConvArgs* A, int batch, hipStream_t stream) {
 template <int CT, int PT, int WC, int WP, bool DEEP>
 int launch_conv_list(const ConvArgs& A, int batch, hipStream_t stream) {
   const int npix = A.ht * A.wt;
-  dim3 grid(sessd_divup(npix * batch, WP * PT * 32) * sessd_divup(A.cout_pad, WC * CT * 32), 1, 1);
+  dim3 grid(sessd_divup(list_launch_pixels(A, npix, batch), WP * PT * 32) * sessd_divup(A.cout_pad, WC * CT * 32), 1, 1);
   SESSD_LAUNCH((conv2d_mfma_kernel<4, CT, PT, WC, WP, DEEP, true>), grid, dim3(256), 0, stream, A);
   SESSD_CHECK_LAUNCH();
   return SESSD_OK;

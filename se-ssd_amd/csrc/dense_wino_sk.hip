@@ -38,6 +38,7 @@
 //   MFMA order per accumulator and round, smallest terms first: a2b0, a1b1, a0b2, a1b0, a0b1, a0b0.
 #include <cstdlib>
 #include "common.hpp"
+#include "bf16_split.hpp"
 
 namespace {
 
@@ -66,17 +67,9 @@ __device__ __forceinline__ float sadd(float a, float b) {
   return r;
 }
 
-// (x0, x1) -> three packed bf16 pairs with x = t0 + t1 + t2 (round to nearest at every step; the residuals are exact in f32)
-__device__ __forceinline__ unsigned pk_bf16(float x0, float x1) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2v){x0, x1}, bf16x2));
-}
-__device__ __forceinline__ void split3_pk(float x0, float x1, unsigned& t0, unsigned& t1, unsigned& t2) {
-  t0 = pk_bf16(x0, x1);
-  x0 -= __builtin_bit_cast(float, t0 << 16); x1 -= __builtin_bit_cast(float, t0 & 0xFFFF0000u);
-  t1 = pk_bf16(x0, x1);
-  x0 -= __builtin_bit_cast(float, t1 << 16); x1 -= __builtin_bit_cast(float, t1 & 0xFFFF0000u);
-  t2 = pk_bf16(x0, x1);
-}
+// the three-way bf16 split of an operand pair (bf16_split.hpp; shared with dense_deconv_split.hip)
+using sessd::pk_bf16;
+using sessd::split3_pk;
 
 struct WinoArgs {
   const float* in;        // (B, cin, H, W)

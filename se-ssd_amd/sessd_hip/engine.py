@@ -38,6 +38,11 @@ def fold_bn(bn):
 # among the autotune's candidates and in the default list configuration. SESSD_WINO_SPLIT=0 leaves it out (A/B runs in one tree).
 WINO_SPLIT = os.environ.get("SESSD_WINO_SPLIT", "1") != "0"
 WINO_LIST_SHAPES = (0, 1, 3) if WINO_SPLIT else (0, 1)
+# The transposed pair over its tile list on the bf16 matrix cores (three-way split operands; csrc/dense_deconv_split.hip): the pair
+# configuration PAIR_SPLIT_CFG beside the direct kernel's tile_cfg 3 / 4 / 11 / 12, among the autotune's candidates.
+# SESSD_DECONV_SPLIT=0 leaves it out (A/B runs in one tree).
+DECONV_SPLIT = os.environ.get("SESSD_DECONV_SPLIT", "1") != "0"
+PAIR_SPLIT_CFG = 45
 
 SPMIDDLE_LAYERS = [
     ("subm", 4, 16, 3, 1, 0, "subm0"), ("subm", 16, 16, 3, 1, 0, "subm0"),
@@ -751,6 +756,8 @@ class InferenceEngine:
         cfg = dict(self.DEFAULT_ACTIVE_CFG if active_cfg is None else active_cfg)
         for l, (shape, mr) in cfg.items():
             # a Winograd list layer needs its packing for the chosen shape (a missing one is an error, not a fall-back)
+            if l == self.ACTIVE_PAIR and shape == PAIR_SPLIT_CFG and any(pc.wsplit() is None for pc, _, _ in self.ACTIVE_SLOTS[l][1]):
+                raise ValueError("active-tile layer %s: no split weight planes (cin %% 16)" % self.ACTIVE_SLOTS[l][0])
             if l in self.ACTIVE_SK or l == self.ACTIVE_PAIR:
                 continue
             layers = self.ACTIVE_SLOTS[l][1] if l == self.ACTIVE_CONV else (self.ACTIVE_SLOTS[l][1],)
@@ -901,6 +908,11 @@ class InferenceEngine:
                                                                    tile_cfg=cfg))
                     if tt < best[1]:
                         best = ((cfg, 0), tt)
+                if DECONV_SPLIT and pa.wsplit() is not None and pb.wsplit() is not None:
+                    tt = timed(lambda: ops.deconv2d_s2_pair_split_active(x_in, pa, pb, sa, ta_, sb, tb_, True, x_out[0], x_out[1],
+                                                                         self.ta.tile_list[m], self.ta.n_list[m:m + 1], residual_a=tr0))
+                    if tt < best[1]:
+                        best = ((PAIR_SPLIT_CFG, 0), tt)
                 pair_dense_t = dense_t
                 if best[1] < dense_t:
                     pick[l] = best
@@ -1163,8 +1175,12 @@ class InferenceEngine:
             if self._kmarks is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-            ops.deconv2d_s2_pair_active(tr1, pa, pb, sa, ta, sb, tb, True, t["mid0"], t["mid1"], self.ta.tile_list[mp],
-                                        self.ta.n_list[mp:mp + 1], residual_a=tr0, tile_cfg=self.active_cfg[self.ACTIVE_PAIR][0])
+            if self.active_cfg[self.ACTIVE_PAIR][0] == PAIR_SPLIT_CFG:
+                ops.deconv2d_s2_pair_split_active(tr1, pa, pb, sa, ta, sb, tb, True, t["mid0"], t["mid1"], self.ta.tile_list[mp],
+                                                  self.ta.n_list[mp:mp + 1], residual_a=tr0)
+            else:
+                ops.deconv2d_s2_pair_active(tr1, pa, pb, sa, ta, sb, tb, True, t["mid0"], t["mid1"], self.ta.tile_list[mp],
+                                            self.ta.n_list[mp:mp + 1], residual_a=tr0, tile_cfg=self.active_cfg[self.ACTIVE_PAIR][0])
             if self._kmarks is not None:
                 e1.record()
                 self._kmarks.append(("deconv_0+deconv_1", e0, e1))

@@ -1564,6 +1564,8 @@ class PackedConv:
         self._upk = None
         self._upk_sk = [None, None, None, None]
         self._sk = None      # argument block of sessd_conv2d_sk (tile_cfg 30), made when first asked for
+        self._wt = None      # the (cin, cout, 3, 3) weight of a stride-2 transposed conv: the split planes are made from it, on demand
+        self._wsplit = None
         self._registry = None  # RepackRegistry that keeps this object fresh (training step), else None
 
     @property
@@ -1581,6 +1583,17 @@ class PackedConv:
             self._upk_sk[shape] = self._registry.create(make) if self._registry is not None else make()
         return self._upk_sk[shape]
 
+
+    def wsplit(self):
+        """A ConvTranspose2d(3, 2, 1, 1) weight as three bf16 planes for sessd_deconv2d_s2_pair_split_active
+        (pack_deconv2d_s2_split), made when first asked for; None if the layer is not eligible (not that layer kind, cin % 16)."""
+        if self._wt is None or self.cin % 16:
+            return None
+        if self._registry is not None:   # a training step's weights change under the registry, which has no job for this packing
+            return pack_deconv2d_s2_split(self._wt)
+        if self._wsplit is None:
+            self._wsplit = pack_deconv2d_s2_split(self._wt)
+        return self._wsplit
 
     def sk_args(self):
         """Host-side argument block of sessd_conv2d_sk (tile_cfg 30): the launches' weights re-packed in the kernel's LDS image
@@ -1916,6 +1929,7 @@ def pack_deconv2d_s2(weight):
                                  dx=torch.tensor([t[3] for t in taps], dtype=torch.int32), in_mul=1, out_mul=2, py=py,
                                  px=px, ntaps=len(taps), view=(w, 9, co * 9, offs)))
     pc = PackedConv(launches, ci, co, "deconv", 2)
+    pc._wt = w
     # host-side argument blocks of the single merged launch (sessd_deconv2d_s2_mfma)
     import ctypes
     pc.wpk4 = (ctypes.c_void_p * 4)(*[la["wpk"].data_ptr() for la in launches])
@@ -1926,6 +1940,51 @@ def pack_deconv2d_s2(weight):
         pc.dy4[c, :la["ntaps"]] = la["dy"]
         pc.dx4[c, :la["ntaps"]] = la["dx"]
     return pc
+
+
+# taps (ky, kx) of a ConvTranspose2d(3, 2, 1, 1) weight in the order dense_deconv_split.hip uses them: grouped by the input pixel
+# (y + ey, x + ex) they multiply -- e = (0,0): W11 W12 W21 W22, (0,1): W10 W20, (1,0): W01 W02, (1,1): W00
+DECONV_SPLIT_TAPS = ((1, 1), (1, 2), (2, 1), (2, 2), (1, 0), (2, 0), (0, 1), (0, 2), (0, 0))
+
+
+def pack_deconv2d_s2_split(weight):
+    """nn.ConvTranspose2d(Cin, Cout, 3, 2, 1, 1) weight (Cin, Cout, 3, 3), Cin % 16 == 0, for sessd_deconv2d_s2_pair_split_active:
+    w = w0 + w1 + w2 EXACTLY with three bfloat16 terms (each rounded to nearest from the f32 residual of the one before), stored
+    [ceil(Cout/128)][Cin/16][tap 9: DECONV_SPLIT_TAPS][plane 3][(cout/32)%4][lane = (cin/8)%2 * 32 + cout%32][cin%8] -- a wave's
+    A fragment of a (k-step, tap, plane) is 16 contiguous bytes per lane. Couts beyond Cout are zero. Once per model (plain
+    torch, on the weight's device)."""
+    w = weight.detach().to(torch.float32)
+    ci, co, kh, kw = w.shape
+    if kh != 3 or kw != 3 or ci % 16:
+        raise ValueError("pack_deconv2d_s2_split: a (Cin, Cout, 3, 3) weight with Cin % 16 == 0")
+    ng = (co + 127) // 128
+    wt = torch.zeros((9, ci, ng * 128), dtype=torch.float32, device=w.device)
+    for t, (ky, kx) in enumerate(DECONV_SPLIT_TAPS):
+        wt[t, :, :co] = w[:, :, ky, kx]
+    planes = []
+    for _ in range(3):
+        p = wt.to(torch.bfloat16)
+        planes.append(p)
+        wt = wt - p.to(torch.float32)   # exact: the residual of a round-to-nearest bf16 fits f32
+    pl = torch.stack(planes).view(3, 9, ci // 16, 2, 8, ng, 4, 32)   # plane, tap, k-step, cin half, cin % 8, group, cout block, cout % 32
+    return pl.permute(5, 2, 1, 0, 6, 3, 7, 4).contiguous().view(ng, ci // 16, 9, 3, 4, 64, 8)
+
+
+def deconv2d_s2_pair_split_active(x, pc_a, pc_b, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, tile_list, n_list, residual_a=None,
+                                  residual_b=None):
+    """sessd_deconv2d_s2_pair_split_active: deconv2d_s2_pair_active on the bf16 matrix cores (three-way split operands, f32
+    accuracy) -- the listed 2x2 tiles of the INPUT map give 4x4 blocks of both outputs, the other output pixels are left alone."""
+    _req(x, torch.float32, "x"); _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
+    B, ci, H, W = x.shape
+    assert pc_a.kind == pc_b.kind == "deconv" and pc_a.cin == pc_b.cin == ci and pc_a.cout == pc_b.cout
+    wa, wb = pc_a.wsplit(), pc_b.wsplit()
+    if wa is None or wb is None:
+        raise ValueError("deconv2d_s2_pair_split_active needs cin % 16 == 0")
+    check(lib.sessd_deconv2d_s2_pair_split_active(x.data_ptr(), B, ci, H, W, wa.data_ptr(), wb.data_ptr(), out_a.data_ptr(), out_b.data_ptr(),
+                                                  pc_a.cout, _p(scale_a), _p(shift_a), _p(scale_b), _p(shift_b), 1 if relu else 0,
+                                                  _p(residual_a), _p(residual_b), tile_list.data_ptr(), n_list.data_ptr(),
+                                                  tile_list.numel(), _stream()), "deconv2d_s2_pair_split_active")
+    return out_a, out_b
 
 
 def pack_deconv2d_ks(weight, s):

@@ -609,6 +609,11 @@ class InferenceEngine:
         if self._tuning_sparse is not None and not dense:
             self._tuning_sparse.append((idx, lay, in_feat, nbr, tm, out_li, out_feat))
 
+    def _need_sk_ws(self, nbytes):
+        """The engine's stream-K workspace holds at least nbytes: a fresh zeroed buffer if it did not (it never shrinks)."""
+        if self.sk_ws is None or self.sk_ws.numel() < nbytes:
+            self.sk_ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.dev)
+
     def _branch_sets(self, shape):
         """conv_0 / conv_1 as two weight sets of one launch: packed U back to back, BatchNorm constants stacked (made once)."""
         key = "_sets%d" % shape
@@ -618,8 +623,8 @@ class InferenceEngine:
             u0, u1 = p0.upk_sk(shape), p1.upk_sk(shape)
             ok = u0 is not None and u1 is not None and p0.cout == p1.cout == 128 and p0.cin == p1.cin and s0 is not None and s1 is not None
             need = int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(2 * self.B, self.H, self.W, 128, shape, 0)) if ok else 0
-            if ok and self.sk_ws is not None and self.sk_ws.numel() < need:
-                self.sk_ws = torch.zeros(need, dtype=torch.uint8, device=self.dev)
+            if ok and self.sk_ws is not None:
+                self._need_sk_ws(need)
             setattr(self, key, dict(upk=torch.cat([u0.reshape(-1), u1.reshape(-1)]), scale=torch.stack([s0, s1]).contiguous(),
                                     shift=torch.stack([t0, t1]).contiguous()) if ok else None)
         return getattr(self, key)
@@ -735,9 +740,7 @@ class InferenceEngine:
             # an RPN engine: its 3x3 layers on the stream-K Winograd kernel (8 waves x 128 couts, exact f32) where they run as
             # full-map launches, and every layer over its tile list with the given (shape, minimum share) choices
             self.tile_cfg.update({"blk0.%d" % i: 22 for i in range(len(self.dn.layers))})
-            need = max(int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(self.B, self.H, self.W, 128, sh, 0)) for sh in (0, 1))
-            if self.sk_ws is None or self.sk_ws.numel() < need:
-                self.sk_ws = torch.zeros(need, dtype=torch.uint8, device=self.dev)
+            self._need_sk_ws(max(int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(self.B, self.H, self.W, 128, sh, 0)) for sh in (0, 1)))
             cfg = dict(self.DEFAULT_ACTIVE_CFG if active_cfg is None else active_cfg)
             for l, (shape, mr) in cfg.items():
                 if l not in self.ACTIVE_SLOTS:
@@ -749,10 +752,8 @@ class InferenceEngine:
         self.tile_cfg.update({"b0.0": 22, "b0.1": 22, "b0.2": 23, "b1.0": 30, "b1.1": 23, "b1.2": 22, "trans_0": 30, "trans_1": 30,
                               "conv_0": 22, "conv_1": 22})
         B = self.B
-        need = max([int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(2 * B, self.H, self.W, 256, sh, 0)) for sh in (0, 1)] +
-                   [int(lib.sessd_conv2d_sk_workspace_bytes(B, self.H, self.W, 256, 1, 0))])
-        if self.sk_ws is None or self.sk_ws.numel() < need:
-            self.sk_ws = torch.zeros(need, dtype=torch.uint8, device=self.dev)
+        self._need_sk_ws(max([int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(2 * B, self.H, self.W, 256, sh, 0)) for sh in (0, 1)] +
+                             [int(lib.sessd_conv2d_sk_workspace_bytes(B, self.H, self.W, 256, 1, 0))]))
         cfg = dict(self.DEFAULT_ACTIVE_CFG if active_cfg is None else active_cfg)
         for l, (shape, mr) in cfg.items():
             # a Winograd list layer needs its packing for the chosen shape (a missing one is an error, not a fall-back)
@@ -817,9 +818,9 @@ class InferenceEngine:
             pc, scale, shift = layer
             best = (None, 1e30)
             cands = list(candidates)
-            if pc.kind == "conv" and pc.stride == 1 and pc.launches[0]["ntaps"] == 9 and pc.cin % 16 == 0:
+            if pc.is_3x3_s1 and pc.cin % 16 == 0:
                 cands.append(10)  # activation-stationary LDS variant
-                if getattr(pc, "upk", None) is not None and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and self.allow_winograd:
+                if pc.upk is not None and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and self.allow_winograd:
                     cands.append(20)  # fused Winograd F(2x2,3x3)
                     if pc.cin % 32 == 0:
                         cands.append(21)  # same, operands fetched two rounds ahead
@@ -829,18 +830,12 @@ class InferenceEngine:
                     # measured 81 / 96 us against 63 / 66 us for 22 / 23 on the two SSFA shapes, profiles/r4_wino_rk_probe.json)
                     for cfg, shape in ((22, 0), (23, 1)) + (((25, 3),) if WINO_SPLIT else ()) if self.allow_streamk else ():
                         if pc.upk_sk(shape) is not None:
-                            need = int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(x.shape[0], x.shape[2], x.shape[3], pc.cout, shape, 0))
-                            if self.sk_ws is None or self.sk_ws.numel() < need:
-                                self.sk_ws = torch.zeros(need, dtype=torch.uint8, device=x.device)
+                            self._need_sk_ws(int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(x.shape[0], x.shape[2], x.shape[3], pc.cout, shape, 0)))
                             cands.append(cfg)
             # LDS-tiled stream-K implicit GEMM (csrc/dense_conv_sk.hip) for what is not 3x3 stride 1: the stride-2 conv, the 1x1
             # convs, the transposed convs (four parity classes in one launch). Shares the engine's stream-K workspace.
-            if self.allow_streamk and pc.cout > 32 and not (pc.kind == "conv" and pc.stride == 1 and pc.launches[0]["ntaps"] == 9) \
-                    and pc.sk_args() is not None:
-                th, tw = (out.shape[2], out.shape[3]) if pc.kind == "conv" else (x.shape[2], x.shape[3])
-                need = int(lib.sessd_conv2d_sk_workspace_bytes(x.shape[0], th, tw, pc.cout, len(pc.launches), 0))
-                if self.sk_ws is None or self.sk_ws.numel() < need:
-                    self.sk_ws = torch.zeros(need, dtype=torch.uint8, device=x.device)
+            if self.allow_streamk and pc.cout > 32 and not pc.is_3x3_s1 and pc.sk_args() is not None:
+                self._need_sk_ws(int(lib.sessd_conv2d_sk_workspace_bytes(x.shape[0], *pc.tile_hw(*x.shape[2:]), pc.cout, len(pc.launches), 0)))
                 cands.append(30)
             if pc.kind == "deconv":
                 cands += [40, 41, 42]  # both px classes of a row parity in every wave: whole-line stores, shared input loads (same bits)
@@ -934,9 +929,7 @@ class InferenceEngine:
                 for shape in WINO_LIST_SHAPES:
                     if p0.upk_sk(shape) is None or p1.upk_sk(shape) is None:
                         continue
-                    need = int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(self.B, self.H, self.W, p0.cout, shape, 0))
-                    if self.sk_ws is None or self.sk_ws.numel() < need:
-                        self.sk_ws = torch.zeros(need, dtype=torch.uint8, device=self.dev)
+                    self._need_sk_ws(int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(self.B, self.H, self.W, p0.cout, shape, 0)))
                     for mr in (4, 8, 16, -1):
                         def both(shape=shape, mr=mr):
                             for (pc_, sc_, sh_), xi, xo in ((layer[0], x_in[0], x_out[0]), (layer[1], x_in[1], x_out[1])):
@@ -952,16 +945,14 @@ class InferenceEngine:
                 continue
             pc, scale, shift = layer
             if l in self.ACTIVE_SK:
-                if pc.launches[0]["ntaps"] == 1 and pc.cin % 8 == 0:
+                if pc.launches[0].ntaps == 1 and pc.cin % 8 == 0:
                     for cfg in (3, 4, 11, 12):
                         tt = timed(lambda: ops.conv2d_mfma_active(x_in, pc, scale, shift, True, x_out, self.ta.tile_list[m],
                                                                   self.ta.n_list[m:m + 1], tile_cfg=cfg))
                         if tt < best[1]:
                             best = ((cfg, 0), tt)
                 if pc.sk_args() is not None:
-                    need = int(lib.sessd_conv2d_sk_workspace_bytes(self.B, x_out.shape[2], x_out.shape[3], pc.cout, len(pc.launches), 0))
-                    if self.sk_ws is None or self.sk_ws.numel() < need:
-                        self.sk_ws = torch.zeros(need, dtype=torch.uint8, device=self.dev)
+                    self._need_sk_ws(int(lib.sessd_conv2d_sk_workspace_bytes(self.B, *pc.tile_hw(*x_in.shape[2:]), pc.cout, len(pc.launches), 0)))
                     for mr in (1, 4, 8, 16):
                         tt = timed(lambda: ops.conv2d_sk_active(x_in, pc, scale, shift, True, x_out, self.sk_ws, self.ta.tile_list[m],
                                                                 self.ta.n_list[m:m + 1], workgroups=self._wgs(2), min_rounds=mr))
@@ -971,9 +962,7 @@ class InferenceEngine:
                 for shape in WINO_LIST_SHAPES:
                     if pc.upk_sk(shape) is None:
                         continue
-                    need = int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(self.B, x_in.shape[2], x_in.shape[3], pc.cout, shape, 0))
-                    if self.sk_ws is None or self.sk_ws.numel() < need:
-                        self.sk_ws = torch.zeros(need, dtype=torch.uint8, device=self.dev)
+                    self._need_sk_ws(int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(self.B, x_in.shape[2], x_in.shape[3], pc.cout, shape, 0)))
                     for mr in self.list_share_candidates:
                         tt = timed(lambda: ops.conv2d_winograd_sk_active(x_in, pc.upk_sk(shape), pc.cout, scale, shift, True, x_out, shape,
                                                                          self.sk_ws, self.ta.tile_list[m], self.ta.n_list[m:m + 1],

@@ -3,6 +3,7 @@
 torch is plumbing only (device memory + the current HIP stream). Inputs must be contiguous CUDA
 tensors of the stated dtype; nothing here copies to the host or synchronises.
 """
+import ctypes
 import os
 
 import torch
@@ -16,6 +17,11 @@ def _stream():
 
 def _p(t):
     return 0 if t is None else t.data_ptr()
+
+
+def _addr(arr):
+    """address of a ctypes array, as the integer the C entries take for a host pointer"""
+    return ctypes.cast(arr, ctypes.c_void_p).value
 
 
 def _req(t, dtype, name):
@@ -900,10 +906,7 @@ class RepackRegistry:
             self.objects[key] = obj
             self.versions[id(weight)] = [weight, weight._version]
             if isinstance(obj, PackedConv):
-                obj._registry = self
-                for la in obj.launches:
-                    if isinstance(la, _Launch):
-                        la["_registry"] = self
+                obj._registry = self   # its lazily made packings (and its launches', through their owner) go through create()
         return obj
 
     def create(self, factory):
@@ -1554,35 +1557,86 @@ def sparse_conv_wgrad(in_feat, grad_out, nbr, tile_mask, n_out_dev, cin, cout):
 
 
 # ------------------------------------------------------------------ dense BEV convolutions
-class PackedConv:
-    """A conv layer lowered to one or more sessd_conv2d_mfma launches (weights in MFMA fragment order)."""
+class Launch:
+    """One sessd_conv2d_mfma launch of a PackedConv: the taps' input offsets dy / dx (int32 host tensors), the step of its tile
+    space in the input (in_mul) and output (out_mul) maps, the output parity class (py, px) it writes, and `view` = (weight,
+    out_stride, in_stride, tap offsets): the strided view of the stored weight that its packings are made from.
+    wpk, the weight in MFMA fragment order, is packed when first read: a 3x3 stride-1 layer that runs on a Winograd kernel never
+    needs it (21 wasted pack launches per training iteration before)."""
+    __slots__ = ("dy", "dx", "in_mul", "out_mul", "py", "px", "ntaps", "view", "_wpk", "_owner")
 
-    def __init__(self, launches, cin, cout, kind, stride):
-        self.launches = launches  # list of dict(wpk, dy, dx, in_mul, out_mul, py, px, ntaps)
+    def __init__(self, dy, dx, in_mul, out_mul, py, px, view):
+        self.dy, self.dx, self.in_mul, self.out_mul, self.py, self.px, self.view = dy, dx, in_mul, out_mul, py, px, view
+        self.ntaps = len(view[3])
+        self._wpk = self._owner = None   # the owner is the PackedConv that takes the launch
+
+    @property
+    def wpk(self):
+        if self._wpk is None:
+            pc = self._owner
+            self._wpk = pc._make(lambda: _pack_taps_view(*self.view, pc.cout, pc.cin))
+        return self._wpk
+
+
+class PackedConv:
+    """A conv layer lowered to one or more sessd_conv2d_mfma launches, with every other packing of its weight that a dense kernel
+    family takes. kind "conv": Conv2d(k in {1, 3}, stride, padding k // 2), one launch; "deconv": ConvTranspose2d(3, 2, 1, 1), one
+    launch per output parity class; "deconv_ks": ConvTranspose2d(s, stride s), s * s one-tap launches.
+    w3 = (weight, adjoint) of a 3x3 stride-1 conv: what the Winograd packings are made from, on demand; wt = the (cin, cout, 3, 3)
+    weight of a "deconv": its launches are packed now, for the argument block of the merged launch, the split planes on demand."""
+
+    def __init__(self, launches, cin, cout, kind, stride, w3=None, wt=None):
+        self.launches = launches  # list of Launch
         self.cin, self.cout, self.kind, self.stride = cin, cout, kind, stride
-        self._w3 = None      # (weight, adjoint): the 3x3 stride-1 weight the Winograd packings are made from, on demand
+        self._w3, self._wt = w3, wt
         self._upk = None
         self._upk_sk = [None, None, None, None]
         self._sk = None      # argument block of sessd_conv2d_sk (tile_cfg 30), made when first asked for
-        self._wt = None      # the (cin, cout, 3, 3) weight of a stride-2 transposed conv: the split planes are made from it, on demand
         self._wsplit = None
         self._registry = None  # RepackRegistry that keeps this object fresh (training step), else None
+        for la in launches:
+            la._owner = self
+        self.wpk4 = self.ntaps4 = self.dy4 = self.dx4 = None
+        if wt is not None:   # host-side argument blocks of the single merged launch (sessd_deconv2d_s2_mfma)
+            self.wpk4 = (ctypes.c_void_p * 4)(*[la.wpk.data_ptr() for la in launches])
+            self.ntaps4 = torch.tensor([la.ntaps for la in launches], dtype=torch.int32)
+            self.dy4 = torch.zeros((4, 4), dtype=torch.int32)
+            self.dx4 = torch.zeros((4, 4), dtype=torch.int32)
+            for c, la in enumerate(launches):
+                self.dy4[c, :la.ntaps] = la.dy
+                self.dx4[c, :la.ntaps] = la.dx
+
+    def _make(self, make):
+        """Make a packing now -- through the registry, which records it as a job of its batched re-pack, if there is one."""
+        return self._registry.create(make) if self._registry is not None else make()
+
+    def out_hw(self, H, W):
+        """(Ho, Wo) of the layer on an (H, W) map"""
+        s = self.stride
+        return ((H + s - 1) // s, (W + s - 1) // s) if self.kind == "conv" else (s * H, s * W)
+
+    def tile_hw(self, H, W):
+        """The pixel space the launches cut their tiles from: the output map of a conv, the INPUT map of a transposed conv (each of
+        its launches writes one output parity class)."""
+        return self.out_hw(H, W) if self.kind == "conv" else (H, W)
+
+    @property
+    def is_3x3_s1(self):
+        """a 3x3 stride-1 conv: the layers the Winograd kernels (tile_cfg 20 - 25) and the LDS variant (10) are written for"""
+        return self._w3 is not None
 
     @property
     def upk(self):
         """U = G g G^T packed for sessd_conv3x3_winograd (tile_cfg 20 / 21); None if the layer is not eligible."""
-        if self._upk is None and self._w3 is not None and self.cin % 8 == 0:
-            make = lambda: pack_winograd(self._w3[0], adjoint=self._w3[1])
-            self._upk = self._registry.create(make) if self._registry is not None else make()
+        if self._upk is None and self.is_3x3_s1 and self.cin % 8 == 0:
+            self._upk = self._make(lambda: pack_winograd(self._w3[0], adjoint=self._w3[1]))
         return self._upk
 
     def upk_sk(self, shape):
         """U packed for sessd_conv3x3_winograd_sk (tile_cfg 22 / 23 / 24 / 25 = shape 0 / 1 / 2 / 3); None if not eligible."""
-        if self._upk_sk[shape] is None and self._w3 is not None and self.cin % (16, 8, 16, 16)[shape] == 0:
-            make = lambda: pack_winograd_sk(self._w3[0], shape, adjoint=self._w3[1])
-            self._upk_sk[shape] = self._registry.create(make) if self._registry is not None else make()
+        if self._upk_sk[shape] is None and self.is_3x3_s1 and self.cin % (16, 8, 16, 16)[shape] == 0:
+            self._upk_sk[shape] = self._make(lambda: pack_winograd_sk(self._w3[0], shape, adjoint=self._w3[1]))
         return self._upk_sk[shape]
-
 
     def wsplit(self):
         """A ConvTranspose2d(3, 2, 1, 1) weight as three bf16 planes for sessd_deconv2d_s2_pair_split_active
@@ -1597,34 +1651,32 @@ class PackedConv:
 
     def sk_args(self):
         """Host-side argument block of sessd_conv2d_sk (tile_cfg 30): the launches' weights re-packed in the kernel's LDS image
-        (one launch each) + tap tables; None if the layer is not eligible (cin % 16, a launch without its weight view)."""
+        (one launch each) + tap tables; None if the layer is not eligible (cin % 16, more than four launches)."""
         if self._sk is None:
-            import ctypes
             n = len(self.launches)
-            if self.cin % 16 or n > 4 or any("view" not in la or la["ntaps"] > 9 for la in self.launches):
+            if self.cin % 16 or n > 4:
                 return None
             ncg = (self.cout + 127) // 128
             wpk, dy, dx = [], (ctypes.c_int * (9 * n))(), (ctypes.c_int * (9 * n))()
             for c, la in enumerate(self.launches):
-                w, so, sc, taps = la["view"]
+                w, so, sc, taps = la.view
                 nt = len(taps)
                 out = torch.empty((ncg, self.cin // 16, nt, 2048), dtype=torch.float32, device=w.device)
                 check(lib.sessd_conv2d_sk_pack(w.data_ptr(), int(so), int(sc), (ctypes.c_int * nt)(*[int(t) for t in taps]), nt,
                                                self.cout, self.cin, out.data_ptr(), _stream()), "conv2d_sk_pack")
                 wpk.append(out)
                 for t in range(nt):
-                    dy[9 * c + t], dx[9 * c + t] = int(la["dy"][t]), int(la["dx"][t])
+                    dy[9 * c + t], dx[9 * c + t] = int(la.dy[t]), int(la.dx[t])
             self._sk = dict(wpk=wpk, wptr=(ctypes.c_void_p * n)(*[t.data_ptr() for t in wpk]),
-                            ntaps=(ctypes.c_int * n)(*[la["ntaps"] for la in self.launches]), dy=dy, dx=dx,
-                            py=(ctypes.c_int * n)(*[la["py"] for la in self.launches]),
-                            px=(ctypes.c_int * n)(*[la["px"] for la in self.launches]), n=n)
+                            ntaps=(ctypes.c_int * n)(*[la.ntaps for la in self.launches]), dy=dy, dx=dx,
+                            py=(ctypes.c_int * n)(*[la.py for la in self.launches]),
+                            px=(ctypes.c_int * n)(*[la.px for la in self.launches]), n=n)
         return self._sk
 
 
 def _pack_taps_view(w, out_stride, in_stride, tap_offsets, cout, cin):
     """One launch (sessd_conv2d_pack_taps): [cin/2][ntaps][2][cout_pad32] with out[kp][t][h][o] = w.flat[o * out_stride +
     (2 kp + h) * in_stride + tap_offsets[t]] -- a transposed / flipped / tap-selected view of the stored weight, no intermediate."""
-    import ctypes
     _req(w, torch.float32, "weight")
     nt = len(tap_offsets)
     cp = (cout + 31) // 32 * 32
@@ -1634,20 +1686,6 @@ def _pack_taps_view(w, out_stride, in_stride, tap_offsets, cout, cin):
     _repack_note("dense", w=w, out=out, so=int(out_stride), sc=int(in_stride), taps=[int(t) for t in tap_offsets], cout=int(cout),
                  cin=int(cin), kind=0, flip=0, layout=0)
     return out
-
-
-class _Launch(dict):
-    """A PackedConv launch whose fragment-order weight ("wpk") is packed when first asked for: a 3x3 stride-1 layer that runs on a
-    Winograd kernel never needs it (21 wasted pack launches per training iteration before)."""
-
-    def __missing__(self, key):
-        if key != "wpk":
-            raise KeyError(key)
-        w, so, sc, taps = self["view"]
-        make = lambda: _pack_taps_view(w, so, sc, taps, self["_co"], self["_ci"])
-        reg = dict.get(self, "_registry")
-        self["wpk"] = reg.create(make) if reg is not None else make()
-        return self["wpk"]
 
 
 def _conv_view(w, adjoint):
@@ -1672,12 +1710,9 @@ def pack_conv2d(weight, stride=1, padding=None, adjoint=False):
     dy = [ky - pad for ky in range(kh) for kx in range(kw)]
     dx = [kx - pad for ky in range(kh) for kx in range(kw)]
     taps = [(kk - 1 - t) if flip else t for t in range(kk)]
-    la = _Launch(dy=torch.tensor(dy, dtype=torch.int32), dx=torch.tensor(dx, dtype=torch.int32), in_mul=stride,
-                 out_mul=1, py=0, px=0, ntaps=kh * kw, view=(w, so, sc, taps), _co=co, _ci=ci)
-    pc = PackedConv([la], ci, co, "conv", stride)
-    if kh == 3 and stride == 1:
-        pc._w3 = (w, bool(adjoint))  # Winograd packings (tile_cfg 20-23) are made when first asked for
-    return pc
+    la = Launch(torch.tensor(dy, dtype=torch.int32), torch.tensor(dx, dtype=torch.int32), stride, 1, 0, 0, (w, so, sc, taps))
+    # nothing is packed here: the launch's weight and the Winograd packings (tile_cfg 20 - 25) are made when first asked for
+    return PackedConv([la], ci, co, "conv", stride, w3=(w, bool(adjoint)) if kh == 3 and stride == 1 else None)
 
 
 def _winograd_pack(weight, layout, adjoint):
@@ -1724,6 +1759,22 @@ _SK_WS = {}
 _SK_WS_RETIRED = []
 
 
+def _sk_workspace(workspace, need, kind, workgroups, device):
+    """The stream-K workspace of a conv2d() launch that takes `need` bytes: the caller's, refused before anything is launched if
+    it is too small; without one the buffer of the per-(device, stream and capture, kernel kind, workgroups) cache, grown to need."""
+    if workspace is not None:
+        if workspace.numel() < need:
+            raise ValueError("conv2d: stream-K workspace too small (%d < %d bytes)" % (workspace.numel(), need))
+        return workspace
+    key = (device.index, _cache_scope(), kind, workgroups)
+    workspace = _SK_WS.get(key)
+    if workspace is None or workspace.numel() < need:
+        if workspace is not None:
+            _SK_WS_RETIRED.append(workspace)  # a captured graph may still point at it: never hand its memory back
+        workspace = _SK_WS[key] = torch.zeros(need, dtype=torch.uint8, device=device)
+    return workspace
+
+
 def winograd_sk_workspace(batch, h, w, cout, device, workgroups=0, shape=0):
     """Zeroed workspace of sessd_conv3x3_winograd_sk (partial-unit scratch + counters)."""
     with torch.cuda.device(device):
@@ -1766,29 +1817,27 @@ def conv2d_winograd_sk_active(x, upk, cout, scale, shift, relu, out, shape, work
     return out
 
 
+def _sk_layer_args(x, pc, sk, epi, out):
+    """what sessd_conv2d_sk and sessd_conv2d_sk_active both begin with: the layer (sk = pc.sk_args()), its maps and its epilogue
+    epi = (scale, shift, relu, residual) as the C entries take them"""
+    B, ci, H, W = x.shape
+    la = pc.launches[0]
+    return (x.data_ptr(), B, ci, H, W, sk["n"], _addr(sk["wptr"]), _addr(sk["ntaps"]), _addr(sk["dy"]), _addr(sk["dx"]), la.in_mul,
+            *pc.tile_hw(H, W), out.data_ptr(), pc.cout, *pc.out_hw(H, W), la.out_mul, _addr(sk["py"]), _addr(sk["px"]), *epi)
+
+
 def conv2d_sk_active(x, pc, scale, shift, relu, out, workspace, tile_list, n_list, workgroups=0, residual=None, min_rounds=4):
     """sessd_conv2d_sk_active: the LDS-tiled stream-K layer (tile_cfg 30: stride-2 / 1x1 conv, or the four classes of a transposed
     conv) over the listed 2x2 tiles of its tile space only (entries image * (th/2 * tw/2) + tile, count on the device); the other
     output pixels of `out` are left alone."""
-    import ctypes
     _req(x, torch.float32, "x"); _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
-    B, ci, H, W = x.shape
     sk = pc.sk_args()
     if sk is None:
         raise ValueError("conv2d_sk_active needs cin % 16 == 0")
-    if pc.kind == "conv":
-        Ho, Wo = (H + pc.stride - 1) // pc.stride, (W + pc.stride - 1) // pc.stride
-        th, tw = Ho, Wo
-    else:
-        Ho, Wo, th, tw = 2 * H, 2 * W, H, W
-    la = pc.launches[0]
-    check(lib.sessd_conv2d_sk_active(x.data_ptr(), B, ci, H, W, sk["n"], ctypes.cast(sk["wptr"], ctypes.c_void_p).value,
-                                     ctypes.cast(sk["ntaps"], ctypes.c_void_p).value, ctypes.cast(sk["dy"], ctypes.c_void_p).value,
-                                     ctypes.cast(sk["dx"], ctypes.c_void_p).value, la["in_mul"], th, tw, out.data_ptr(), pc.cout,
-                                     Ho, Wo, la["out_mul"], ctypes.cast(sk["py"], ctypes.c_void_p).value,
-                                     ctypes.cast(sk["px"], ctypes.c_void_p).value, _p(scale), _p(shift), 1 if relu else 0,
-                                     _p(residual), tile_list.data_ptr(), n_list.data_ptr(), tile_list.numel(), int(min_rounds),
-                                     workspace.data_ptr(), workspace.numel(), int(workgroups), _stream()), "conv2d_sk_active")
+    epi = (_p(scale), _p(shift), 1 if relu else 0, _p(residual))
+    check(lib.sessd_conv2d_sk_active(*_sk_layer_args(x, pc, sk, epi, out), tile_list.data_ptr(), n_list.data_ptr(), tile_list.numel(),
+                                     int(min_rounds), workspace.data_ptr(), workspace.numel(), int(workgroups), _stream()),
+          "conv2d_sk_active")
     return out
 
 
@@ -1797,29 +1846,35 @@ def conv2d_mfma_active(x, pc, scale, shift, relu, out, tile_list, n_list, tile_c
     computed pixels carry the bits of the plain launch."""
     _req(x, torch.float32, "x"); _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
     B, ci, H, W = x.shape
-    assert pc.kind == "conv" and pc.stride == 1 and len(pc.launches) == 1 and pc.launches[0]["ntaps"] == 1 and ci % 8 == 0
+    assert pc.kind == "conv" and pc.stride == 1 and len(pc.launches) == 1 and pc.launches[0].ntaps == 1 and ci % 8 == 0
     la = pc.launches[0]
-    check(lib.sessd_conv2d_mfma_active(x.data_ptr(), B, ci, H, W, la["wpk"].data_ptr(), 1, la["dy"].data_ptr(), la["dx"].data_ptr(), 1, H, W,
+    check(lib.sessd_conv2d_mfma_active(x.data_ptr(), B, ci, H, W, la.wpk.data_ptr(), 1, la.dy.data_ptr(), la.dx.data_ptr(), 1, H, W,
                                        out.data_ptr(), pc.cout, H, W, 1, 0, 0, _p(scale), _p(shift), 1 if relu else 0, _p(residual),
                                        tile_list.data_ptr(), n_list.data_ptr(), tile_list.numel(), int(tile_cfg), _stream()),
           "conv2d_mfma_active")
     return out
 
 
+def _pair_args(x, pc_a, pc_b, weights, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a, residual_b):
+    """what the three launches of a transposed-conv pair begin with: the input, the two layers' `weights` (None: the four classes'
+    packings and the tap tables they share), the outputs and their epilogues"""
+    _req(x, torch.float32, "x")
+    B, ci, H, W = x.shape
+    assert pc_a.kind == pc_b.kind == "deconv" and pc_a.cin == pc_b.cin == ci and pc_a.cout == pc_b.cout
+    if weights is None:
+        weights = (_addr(pc_a.wpk4), _addr(pc_b.wpk4), pc_a.ntaps4.data_ptr(), pc_a.dy4.data_ptr(), pc_a.dx4.data_ptr())
+    return (x.data_ptr(), B, ci, H, W, *weights, out_a.data_ptr(), out_b.data_ptr(), pc_a.cout, _p(scale_a), _p(shift_a), _p(scale_b),
+            _p(shift_b), 1 if relu else 0, _p(residual_a), _p(residual_b))
+
+
 def deconv2d_s2_pair_active(x, pc_a, pc_b, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, tile_list, n_list, residual_a=None,
                             residual_b=None, tile_cfg=11):
     """sessd_deconv2d_s2_mfma_pair_active: deconv2d_s2_pair over the listed 2x2 tiles of the INPUT map only (a listed tile = a 4x4
     block of both outputs); the other output pixels are left alone."""
-    import ctypes
-    _req(x, torch.float32, "x"); _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
-    B, ci, H, W = x.shape
-    assert pc_a.kind == pc_b.kind == "deconv" and pc_a.cin == pc_b.cin == ci and pc_a.cout == pc_b.cout
-    check(lib.sessd_deconv2d_s2_mfma_pair_active(x.data_ptr(), B, ci, H, W, ctypes.cast(pc_a.wpk4, ctypes.c_void_p).value,
-                                                 ctypes.cast(pc_b.wpk4, ctypes.c_void_p).value, pc_a.ntaps4.data_ptr(),
-                                                 pc_a.dy4.data_ptr(), pc_a.dx4.data_ptr(), out_a.data_ptr(), out_b.data_ptr(), pc_a.cout,
-                                                 _p(scale_a), _p(shift_a), _p(scale_b), _p(shift_b), 1 if relu else 0, _p(residual_a),
-                                                 _p(residual_b), tile_list.data_ptr(), n_list.data_ptr(), tile_list.numel(),
-                                                 int(tile_cfg), _stream()), "deconv2d_s2_mfma_pair_active")
+    _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
+    args = _pair_args(x, pc_a, pc_b, None, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a, residual_b)
+    check(lib.sessd_deconv2d_s2_mfma_pair_active(*args, tile_list.data_ptr(), n_list.data_ptr(), tile_list.numel(), int(tile_cfg),
+                                                 _stream()), "deconv2d_s2_mfma_pair_active")
     return out_a, out_b
 
 
@@ -1834,7 +1889,6 @@ class TileActivity:
     row's 128 bits = tile (ty, tx) is computed; rows beyond h/2 unused --, tile_list[s] (batch * H/2 * W/2,) int32, n_list[s]."""
 
     def __init__(self, batch, H, W, steps, device):
-        import ctypes
         steps = [0] * steps if isinstance(steps, int) else [int(v) for v in steps]
         self.batch, self.H, self.W, self.steps = int(batch), int(H), int(W), steps
         self.dims, h, w = [], H, W
@@ -1924,22 +1978,9 @@ def pack_deconv2d_s2(weight):
             taps = [(ky, ey, kx, ex) for (ky, ey) in sel[py] for (kx, ex) in sel[px]]
             # (ci, co, 3, 3) weight: output channel o has element stride 9, input channel c stride co * 9, tap (ky, kx) offset 3 ky + kx
             offs = [3 * ky + kx for (ky, ey, kx, ex) in taps]
-            wpk = _pack_taps_view(w, 9, co * 9, offs, co, ci)
-            launches.append(dict(wpk=wpk, dy=torch.tensor([t[1] for t in taps], dtype=torch.int32),
-                                 dx=torch.tensor([t[3] for t in taps], dtype=torch.int32), in_mul=1, out_mul=2, py=py,
-                                 px=px, ntaps=len(taps), view=(w, 9, co * 9, offs)))
-    pc = PackedConv(launches, ci, co, "deconv", 2)
-    pc._wt = w
-    # host-side argument blocks of the single merged launch (sessd_deconv2d_s2_mfma)
-    import ctypes
-    pc.wpk4 = (ctypes.c_void_p * 4)(*[la["wpk"].data_ptr() for la in launches])
-    pc.ntaps4 = torch.tensor([la["ntaps"] for la in launches], dtype=torch.int32)
-    pc.dy4 = torch.zeros((4, 4), dtype=torch.int32)
-    pc.dx4 = torch.zeros((4, 4), dtype=torch.int32)
-    for c, la in enumerate(launches):
-        pc.dy4[c, :la["ntaps"]] = la["dy"]
-        pc.dx4[c, :la["ntaps"]] = la["dx"]
-    return pc
+            launches.append(Launch(torch.tensor([t[1] for t in taps], dtype=torch.int32), torch.tensor([t[3] for t in taps], dtype=torch.int32),
+                                   1, 2, py, px, (w, 9, co * 9, offs)))
+    return PackedConv(launches, ci, co, "deconv", 2, wt=w)   # (packs the four classes now)
 
 
 # taps (ky, kx) of a ConvTranspose2d(3, 2, 1, 1) weight in the order dense_deconv_split.hip uses them: grouped by the input pixel
@@ -1974,16 +2015,14 @@ def deconv2d_s2_pair_split_active(x, pc_a, pc_b, scale_a, shift_a, scale_b, shif
                                   residual_b=None):
     """sessd_deconv2d_s2_pair_split_active: deconv2d_s2_pair_active on the bf16 matrix cores (three-way split operands, f32
     accuracy) -- the listed 2x2 tiles of the INPUT map give 4x4 blocks of both outputs, the other output pixels are left alone."""
-    _req(x, torch.float32, "x"); _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
-    B, ci, H, W = x.shape
-    assert pc_a.kind == pc_b.kind == "deconv" and pc_a.cin == pc_b.cin == ci and pc_a.cout == pc_b.cout
+    _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
     wa, wb = pc_a.wsplit(), pc_b.wsplit()
     if wa is None or wb is None:
         raise ValueError("deconv2d_s2_pair_split_active needs cin % 16 == 0")
-    check(lib.sessd_deconv2d_s2_pair_split_active(x.data_ptr(), B, ci, H, W, wa.data_ptr(), wb.data_ptr(), out_a.data_ptr(), out_b.data_ptr(),
-                                                  pc_a.cout, _p(scale_a), _p(shift_a), _p(scale_b), _p(shift_b), 1 if relu else 0,
-                                                  _p(residual_a), _p(residual_b), tile_list.data_ptr(), n_list.data_ptr(),
-                                                  tile_list.numel(), _stream()), "deconv2d_s2_pair_split_active")
+    args = _pair_args(x, pc_a, pc_b, (wa.data_ptr(), wb.data_ptr()), scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a,
+                      residual_b)
+    check(lib.sessd_deconv2d_s2_pair_split_active(*args, tile_list.data_ptr(), n_list.data_ptr(), tile_list.numel(), _stream()),
+          "deconv2d_s2_pair_split_active")
     return out_a, out_b
 
 
@@ -2000,11 +2039,11 @@ def pack_deconv2d_ks(weight, s):
     for py in range(s):
         for px in range(s):
             # output channel o has element stride s * s, input channel c stride co * s * s, tap (py, px) offset py * s + px
-            offs = [py * s + px]
-            wpk = _pack_taps_view(w, s * s, co * s * s, offs, co, ci)
-            launches.append(dict(wpk=wpk, dy=zero, dx=zero, in_mul=1, out_mul=s, py=py, px=px, ntaps=1,
-                                 view=(w, s * s, co * s * s, offs)))
-    return PackedConv(launches, ci, co, "deconv_ks", s)
+            launches.append(Launch(zero, zero, 1, s, py, px, (w, s * s, co * s * s, [py * s + px])))
+    pc = PackedConv(launches, ci, co, "deconv_ks", s)
+    for la in launches:
+        la.wpk   # packed now, as pack_deconv2d_s2 does
+    return pc
 
 
 class PackedDeconvKs:
@@ -2060,112 +2099,102 @@ def deconv_ks_slice(x, packed, scale, shift, relu, out, c_off):
 def deconv2d_s2_pair(x, pc_a, pc_b, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a=None, residual_b=None, tile_cfg=4):
     """Two ConvTranspose2d(3, 2, 1, 1) layers of one shape on the SAME input in one launch (sessd_deconv2d_s2_mfma_pair); the same
     bits as two conv2d() calls with that tile_cfg (3, 4, 11 or 12)."""
-    import ctypes
-    _req(x, torch.float32, "x")
-    B, ci, H, W = x.shape
-    assert pc_a.kind == pc_b.kind == "deconv" and pc_a.cin == pc_b.cin == ci and pc_a.cout == pc_b.cout
-    check(lib.sessd_deconv2d_s2_mfma_pair(x.data_ptr(), B, ci, H, W, ctypes.cast(pc_a.wpk4, ctypes.c_void_p).value,
-                                          ctypes.cast(pc_b.wpk4, ctypes.c_void_p).value, pc_a.ntaps4.data_ptr(), pc_a.dy4.data_ptr(),
-                                          pc_a.dx4.data_ptr(), out_a.data_ptr(), out_b.data_ptr(), pc_a.cout, _p(scale_a), _p(shift_a),
-                                          _p(scale_b), _p(shift_b), 1 if relu else 0, _p(residual_a), _p(residual_b), int(tile_cfg),
-                                          _stream()), "deconv2d_s2_mfma_pair")
+    args = _pair_args(x, pc_a, pc_b, None, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a, residual_b)
+    check(lib.sessd_deconv2d_s2_mfma_pair(*args, int(tile_cfg), _stream()), "deconv2d_s2_mfma_pair")
     return out_a, out_b
 
 
+# conv2d's kernel families. Each takes the layer as conv2d does, with `out` allocated, and epi = (scale, shift, relu, residual) as
+# the C entries take them.
+def _conv2d_winograd_sk(x, pc, epi, out, shape, workspace, workgroups):
+    B, ci, H, W = x.shape
+    upk = pc.upk_sk(shape)
+    if upk is None or (H & 1) or (W & 1):
+        raise ValueError("tile_cfg 22/23/24/25 (stream-K Winograd) needs a 3x3 stride-1 conv with cin % 16 (22, 24, 25) / 8 (23) == 0 "
+                         "and even H, W")
+    need = int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(B, H, W, pc.cout, shape, workgroups))
+    workspace = _sk_workspace(workspace, need, shape, workgroups, x.device)
+    check(lib.sessd_conv3x3_winograd_sk(x.data_ptr(), B, ci, H, W, upk.data_ptr(), out.data_ptr(), pc.cout, *epi, workspace.data_ptr(),
+                                        workspace.numel(), shape, workgroups, _stream()), "conv3x3_winograd_sk")
+
+
+def _conv2d_sk(x, pc, epi, out, workspace, workgroups):
+    sk = pc.sk_args()
+    if sk is None:
+        raise ValueError("tile_cfg 30 (LDS-tiled stream-K) needs cin % 16 == 0")
+    need = int(lib.sessd_conv2d_sk_workspace_bytes(x.shape[0], *pc.tile_hw(*x.shape[2:]), pc.cout, sk["n"], workgroups))
+    workspace = _sk_workspace(workspace, need, "csk", workgroups, x.device)
+    check(lib.sessd_conv2d_sk(*_sk_layer_args(x, pc, sk, epi, out), workspace.data_ptr(), workspace.numel(), workgroups, _stream()),
+          "conv2d_sk")
+
+
+def _conv2d_winograd(x, pc, epi, out, variant):
+    B, ci, H, W = x.shape
+    if pc.upk is None or (H & 1) or (W & 1):
+        raise ValueError("tile_cfg 20/21 (Winograd) needs a 3x3 stride-1 conv with cin % 8 == 0 and even H, W")
+    check(lib.sessd_conv3x3_winograd(x.data_ptr(), B, ci, H, W, pc.upk.data_ptr(), out.data_ptr(), pc.cout, *epi, variant, _stream()),
+          "conv3x3_winograd")
+
+
+def _deconv2d_s2_merged(x, pc, epi, out, tile_cfg):
+    B, ci, H, W = x.shape
+    cfg = tile_cfg if tile_cfg is not None else default_tile_cfg(pc.cout, H * W, 4)
+    check(lib.sessd_deconv2d_s2_mfma(x.data_ptr(), B, ci, H, W, _addr(pc.wpk4), pc.ntaps4.data_ptr(), pc.dy4.data_ptr(), pc.dx4.data_ptr(),
+                                     out.data_ptr(), pc.cout, *epi, cfg, _stream()), "deconv2d_s2_mfma")
+
+
+def _conv2d_direct(x, pc, epi, out, tile_cfg):
+    B, ci, H, W = x.shape
+    (Ho, Wo), (th, tw) = pc.out_hw(H, W), pc.tile_hw(H, W)
+    for la in pc.launches:
+        cfg = tile_cfg if tile_cfg is not None else default_tile_cfg(pc.cout, th * tw, la.ntaps)
+        check(lib.sessd_conv2d_mfma(x.data_ptr(), B, ci, H, W, la.wpk.data_ptr(), la.ntaps, la.dy.data_ptr(), la.dx.data_ptr(), la.in_mul,
+                                    th, tw, out.data_ptr(), pc.cout, Ho, Wo, la.out_mul, la.py, la.px, *epi, cfg, _stream()), "conv2d_mfma")
+
+
 def conv2d(x, pc, scale=None, shift=None, relu=True, residual=None, out=None, tile_cfg=None, workspace=None, workgroups=0):
-    """x (B,Cin,H,W) NCHW float32 on the device. Returns (B,Cout,Ho,Wo). tile_cfg 22 = stream-K Winograd: `workspace` from
-    winograd_sk_workspace (one per concurrently running stream); without one a per-(device, stream) cache is used."""
+    """x (B,Cin,H,W) NCHW float32 on the device. Returns (B,Cout,Ho,Wo): the layer + folded BatchNorm (scale, shift) + ReLU +
+    residual. The selectable tile_cfg values, all of them:
+      0 - 8, 11, 12, 13 (every layer kind): wave / workgroup tilings of the direct kernel, sessd_conv2d_mfma, one launch per entry of
+        pc.launches (dispatch_tile in csrc/dense_conv.hip has the shapes; 11 / 12 / 13 = 4 / 3 / 2 with operands fetched two steps ahead).
+        A "deconv" with cin % 8 == 0 runs its four parity classes as ONE launch, sessd_deconv2d_s2_mfma, which refuses 13 and also
+        takes 40 / 41 / 42: both px classes of a row parity in every wave (csrc/dense_deconv_pair.hip).
+      30 ("conv", "deconv"; cin % 16 == 0): LDS-tiled stream-K, sessd_conv2d_sk (csrc/dense_conv_sk.hip), meant for what is not 3x3 stride 1.
+      3x3 stride-1 "conv" only -- 10: activation-stationary LDS variant of the direct kernel, cin % 16 == 0; 20 / 21: Winograd
+        F(2x2,3x3), sessd_conv3x3_winograd, cin % 8 == 0 / 21: operands two rounds ahead, cin % 32 == 0; 22 / 23 / 24 / 25: its stream-K
+        shapes 0 - 3, sessd_conv3x3_winograd_sk (csrc/dense_wino_sk.hip): 8 waves x 128 couts / 4 x 64 / 4 x 128 with the output
+        transform in registers / shape 0 on the bf16 matrix cores, cin % 16 == 0 (23: % 8). All of 20 - 25 need even H, W.
+      A "deconv_ks" runs on the direct kernel only: anything from 20 up is refused.
+    None: default_tile_cfg, or 20 for a 3x3 stride-1 layer on an even map of >= 4096 pixels while USE_WINOGRAD.
+    The stream-K families (22 - 25, 30) take a zeroed `workspace` (winograd_sk_workspace / conv2d_sk_workspace, one per concurrently
+    running stream; too small a one is a ValueError) -- without one a per-(device, stream) cache is used -- and `workgroups`."""
     _req(x, torch.float32, "x")
     B, ci, H, W = x.shape
     assert ci == pc.cin
-    if pc.kind == "conv":
-        Ho, Wo = (H + pc.stride - 1) // pc.stride, (W + pc.stride - 1) // pc.stride
-        th, tw = Ho, Wo
-    elif pc.kind == "deconv_ks":   # kernel size = stride transposed conv: s * s one-tap launches of sessd_conv2d_mfma
-        if tile_cfg is not None and tile_cfg >= 20:
-            raise ValueError("a kernel-size = stride transposed conv runs on the sessd_conv2d_mfma tilings only")
-        Ho, Wo = pc.stride * H, pc.stride * W
-        th, tw = H, W
-    else:
-        Ho, Wo = 2 * H, 2 * W
-        th, tw = H, W
+    if pc.kind == "deconv_ks" and tile_cfg is not None and tile_cfg >= 20:
+        raise ValueError("a kernel-size = stride transposed conv runs on the sessd_conv2d_mfma tilings only")
     if out is None:
-        out = torch.empty((B, pc.cout, Ho, Wo), dtype=torch.float32, device=x.device)
+        out = torch.empty((B, pc.cout, *pc.out_hw(H, W)), dtype=torch.float32, device=x.device)
+    epi = (_p(scale), _p(shift), 1 if relu else 0, _p(residual))
     if tile_cfg in (22, 23, 24, 25):
-        shape = tile_cfg - 22
-        upk = pc.upk_sk(shape) if pc.kind == "conv" else None
-        if upk is None or (H & 1) or (W & 1):
-            raise ValueError("tile_cfg 22/23/24/25 (stream-K Winograd) needs a 3x3 stride-1 conv with cin % 16 (22, 24, 25) / 8 (23) == 0 "
-                             "and even H, W")
-        if workspace is None:
-            key = (x.device.index, _cache_scope(), shape, workgroups)
-            need = int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(B, H, W, pc.cout, shape, workgroups))
-            workspace = _SK_WS.get(key)
-            if workspace is None or workspace.numel() < need:
-                if workspace is not None:
-                    _SK_WS_RETIRED.append(workspace)  # a captured graph may still point at it: never hand its memory back
-                workspace = _SK_WS[key] = torch.zeros(need, dtype=torch.uint8, device=x.device)
-        check(lib.sessd_conv3x3_winograd_sk(x.data_ptr(), B, ci, H, W, upk.data_ptr(), out.data_ptr(), pc.cout, _p(scale),
-                                            _p(shift), 1 if relu else 0, _p(residual), workspace.data_ptr(), workspace.numel(),
-                                            shape, workgroups, _stream()), "conv3x3_winograd_sk")
-        return out
-    if tile_cfg == 30:
-        sk = pc.sk_args()
-        if sk is None:
-            raise ValueError("tile_cfg 30 (LDS-tiled stream-K) needs cin % 16 == 0")
-        la = pc.launches[0]
-        need = int(lib.sessd_conv2d_sk_workspace_bytes(B, th, tw, pc.cout, sk["n"], workgroups))
-        if workspace is None:
-            key = (x.device.index, _cache_scope(), "csk", workgroups)
-            workspace = _SK_WS.get(key)
-            if workspace is None or workspace.numel() < need:
-                if workspace is not None:
-                    _SK_WS_RETIRED.append(workspace)
-                workspace = _SK_WS[key] = torch.zeros(need, dtype=torch.uint8, device=x.device)
-        elif workspace.numel() < need:
-            raise ValueError("conv2d: stream-K workspace too small (%d < %d bytes)" % (workspace.numel(), need))
-        import ctypes
-        check(lib.sessd_conv2d_sk(x.data_ptr(), B, ci, H, W, sk["n"], ctypes.cast(sk["wptr"], ctypes.c_void_p).value,
-                                  ctypes.cast(sk["ntaps"], ctypes.c_void_p).value, ctypes.cast(sk["dy"], ctypes.c_void_p).value,
-                                  ctypes.cast(sk["dx"], ctypes.c_void_p).value, la["in_mul"], th, tw, out.data_ptr(), pc.cout,
-                                  Ho, Wo, la["out_mul"], ctypes.cast(sk["py"], ctypes.c_void_p).value,
-                                  ctypes.cast(sk["px"], ctypes.c_void_p).value, _p(scale), _p(shift), 1 if relu else 0,
-                                  _p(residual), workspace.data_ptr(), workspace.numel(), workgroups, _stream()), "conv2d_sk")
-        return out
-    if tile_cfg in (20, 21):
-        if getattr(pc, "upk", None) is None or (H & 1) or (W & 1):
-            raise ValueError("tile_cfg 20/21 (Winograd) needs a 3x3 stride-1 conv with cin % 8 == 0 and even H, W")
-        check(lib.sessd_conv3x3_winograd(x.data_ptr(), B, ci, H, W, pc.upk.data_ptr(), out.data_ptr(), pc.cout, _p(scale),
-                                         _p(shift), 1 if relu else 0, _p(residual), tile_cfg - 20, _stream()),
-              "conv3x3_winograd")
-        return out
-    if pc.kind == "deconv" and ci % 8 == 0:
-        import ctypes
-        cfg = tile_cfg if tile_cfg is not None else default_tile_cfg(pc.cout, th * tw, 4)
-        check(lib.sessd_deconv2d_s2_mfma(x.data_ptr(), B, ci, H, W, ctypes.cast(pc.wpk4, ctypes.c_void_p).value,
-                                         pc.ntaps4.data_ptr(), pc.dy4.data_ptr(), pc.dx4.data_ptr(), out.data_ptr(),
-                                         pc.cout, _p(scale), _p(shift), 1 if relu else 0, _p(residual), cfg, _stream()),
-              "deconv2d_s2_mfma")
-        return out
-    if tile_cfg is None and USE_WINOGRAD and pc.kind == "conv" and pc._w3 is not None and not (H & 1) and not (W & 1) \
-            and H * W >= 4096 and ci % 8 == 0:
+        _conv2d_winograd_sk(x, pc, epi, out, tile_cfg - 22, workspace, workgroups)
+    elif tile_cfg == 30:
+        _conv2d_sk(x, pc, epi, out, workspace, workgroups)
+    elif tile_cfg in (20, 21):
+        _conv2d_winograd(x, pc, epi, out, tile_cfg - 20)
+    elif pc.kind == "deconv" and ci % 8 == 0:
+        _deconv2d_s2_merged(x, pc, epi, out, tile_cfg)
+    elif tile_cfg is None and USE_WINOGRAD and pc.is_3x3_s1 and not (H & 1) and not (W & 1) and H * W >= 4096 and ci % 8 == 0:
         # The first-generation kernel: every tile block is computed by one workgroup from start to end, so a frame's bits do not
         # depend on its batch slot or on the batch size. The stream-K kernel (tile_cfg 22 / 23, 20 % faster) is deterministic
         # for a fixed (shape, batch, workgroup count) only -- a unit cut between two workgroups adds two partial sums -- and is
         # chosen explicitly: engine.autotune(), the training path.
-        return conv2d(x, pc, scale, shift, relu, residual, out, 20)
-    for la in pc.launches:
-        cfg = tile_cfg
-        if cfg is None:
-            cfg = default_tile_cfg(pc.cout, th * tw, la["ntaps"])
-        check(lib.sessd_conv2d_mfma(x.data_ptr(), B, ci, H, W, la["wpk"].data_ptr(), la["ntaps"], la["dy"].data_ptr(),
-                                    la["dx"].data_ptr(), la["in_mul"], th, tw, out.data_ptr(), pc.cout, Ho, Wo,
-                                    la["out_mul"], la["py"], la["px"], _p(scale), _p(shift), 1 if relu else 0,
-                                    _p(residual), cfg, _stream()), "conv2d_mfma")
+        _conv2d_winograd(x, pc, epi, out, 0)
+    else:
+        _conv2d_direct(x, pc, epi, out, tile_cfg)
     return out
 
 
-_TILE_CFG_OVERRIDE = {}
 # tile_cfg families of the 3x3 stride-1 convs: 20/21 first-generation Winograd F(2x2,3x3), 22/23 its stream-K form
 WINOGRAD_CFGS = (20, 21, 22, 23, 24)
 WINOGRAD_SK_CFGS = (22, 23, 24)   # 24: third generation, output transform in registers (same cuts and bits as 22)
@@ -2397,7 +2426,7 @@ def conv2d_wgrad(inp, grad_out, ksize, stride, winograd=None):
 
 def _train_cfg(pc, x):
     """tile_cfg of the training path: the stream-K Winograd kernel for the 3x3 stride-1 layers it covers, else the default."""
-    ok = (USE_WINOGRAD and pc.kind == "conv" and pc._w3 is not None and pc.cin % 16 == 0 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
+    ok = (USE_WINOGRAD and pc.is_3x3_s1 and pc.cin % 16 == 0 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
           and x.shape[2] * x.shape[3] >= 4096)
     return 22 if ok else None
 
@@ -2445,9 +2474,6 @@ def conv2d_module(x, m):
 
 
 def default_tile_cfg(cout, npix, ntaps):
-    key = (cout, npix, ntaps)
-    if key in _TILE_CFG_OVERRIDE:
-        return _TILE_CFG_OVERRIDE[key]
     # measured on MI355X at batch 1 (engine.autotune() refines per layer): 32c x 32p wave tiles fill the 1024 SIMDs
     # best; pixel-major workgroups (cfg 4) for the 3x3 / 1x1 layers, cout-major (cfg 3) for the merged deconv
     if ntaps == 4 and cout > 32:

@@ -214,7 +214,7 @@ class PillarEngine:
         # every weight packing made now, not by the first frame (PackedConv packs on demand)
         for pc in [L["pc"] for blk in self.blocks for L in blk] + [u["parent"] for u in self.ups] + [self.head_pc]:
             for la in pc.launches:
-                la["wpk"]          # sessd_conv2d_mfma's fragment order
+                la.wpk             # sessd_conv2d_mfma's fragment order
             pc.upk                 # the Winograd form ops.conv2d picks by default for a large 3x3 stride-1 layer (None if not one)
         # ---- predict, as MultiGroupHead.predict passes it: the head's own score threshold and centre range
         mh = model.bbox_head

@@ -358,13 +358,13 @@ def test_device_weight_packers_equal_the_torch_restatement(dev, co, ci):
     g = torch.Generator().manual_seed(co + ci)
     w = torch.randn(co, ci, 3, 3, generator=g).to(dev)
     pc = ops.pack_conv2d(w, 1)
-    assert torch.equal(pc.launches[0]["wpk"], _taps_ref(w.reshape(co, ci, 9)))
+    assert torch.equal(pc.launches[0].wpk, _taps_ref(w.reshape(co, ci, 9)))
     if co % 2 == 0:
         wd = w.flip(2, 3).transpose(0, 1).contiguous()          # (ci, co, 3, 3): the adjoint layer's weight
         pa = ops.pack_conv2d(w, 1, adjoint=True)
-        assert (pa.cin, pa.cout) == (co, ci) and torch.equal(pa.launches[0]["wpk"], _taps_ref(wd.reshape(ci, co, 9)))
+        assert (pa.cin, pa.cout) == (co, ci) and torch.equal(pa.launches[0].wpk, _taps_ref(wd.reshape(ci, co, 9)))
     w1 = torch.randn(co, ci, 1, 1, generator=g).to(dev)
-    assert torch.equal(ops.pack_conv2d(w1).launches[0]["wpk"], _taps_ref(w1.reshape(co, ci, 1)))
+    assert torch.equal(ops.pack_conv2d(w1).launches[0].wpk, _taps_ref(w1.reshape(co, ci, 1)))
     # transposed conv: weight (Cin, Cout, 3, 3)
     wt = torch.randn(ci, co, 3, 3, generator=g).to(dev)
     pd = ops.pack_deconv2d_s2(wt)
@@ -374,7 +374,7 @@ def test_device_weight_packers_equal_the_torch_restatement(dev, co, ci):
         for px in (0, 1):
             taps = [(ky, kx) for (ky, _) in sel[py] for (kx, _) in sel[px]]
             ref = _taps_ref(torch.stack([wt[:, :, ky, kx] for ky, kx in taps], -1).permute(1, 0, 2).contiguous())
-            assert torch.equal(pd.launches[k]["wpk"], ref), (py, px)
+            assert torch.equal(pd.launches[k].wpk, ref), (py, px)
             k += 1
     # Winograd: U = G g G^T (float64, rounded once) in the three layouts
     for adjoint in ((False, True) if co % 2 == 0 else (False,)):
@@ -392,3 +392,68 @@ def test_device_weight_packers_equal_the_torch_restatement(dev, co, ci):
             ref = Up.view(ng, cc // 32, 32, c // 2, 2, nw, 16 // nw).permute(0, 3, 5, 4, 2, 1, 6).contiguous()
             got = ops.pack_winograd_sk(w, shape, adjoint=adjoint)
             assert got.shape == ref.shape and float((got - ref).abs().max()) <= 1.2e-7 * float(U.abs().max())
+
+
+def _layer(dev, cin, cout, k, stride, H, W, B, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, cin, H, W, generator=g)
+    w = torch.randn(cout, cin, k, k, generator=g) * 0.05
+    return x, w, x.to(dev), ops.pack_conv2d(w.to(dev), stride)
+
+
+def test_conv2d_refuses_what_a_family_does_not_cover(dev):
+    """Host-side refusals, before anything is launched: a layer the Winograd / stream-K families do not cover (cin 6), a
+    kernel-size = stride transposed conv on anything but the direct kernel, a caller's stream-K workspace that is too small (a
+    ValueError from Python for both stream-K families). The layers still run afterwards."""
+    x6, w6, xd6, pc6 = _layer(dev, 6, 32, 3, 1, 6, 4, 1, 1)
+    for cfg in (20, 22, 23, 24, 25, 30):
+        with pytest.raises(ValueError):
+            ops.conv2d(xd6, pc6, tile_cfg=cfg)
+    pk = ops.pack_deconv2d_ks(torch.randn(16, 32, 2, 2).to(dev), 2)
+    with pytest.raises(ValueError):
+        ops.conv2d(torch.randn(1, 16, 4, 4).to(dev), pk, tile_cfg=20)
+    x16, w16, xd16, pc16 = _layer(dev, 16, 40, 3, 1, 10, 66, 1, 2)
+    small = torch.zeros(16, dtype=torch.uint8, device=dev)
+    for cfg in (22, 30):
+        with pytest.raises(ValueError):
+            ops.conv2d(xd16, pc16, tile_cfg=cfg, workspace=small)
+    assert not bool(small.any())
+    for x, w, xd, pc in ((x6, w6, xd6, pc6), (x16, w16, xd16, pc16)):
+        _close(ops.conv2d(xd, pc, relu=False, tile_cfg=4).cpu(), F.conv2d(x, w, padding=1))
+
+
+@pytest.mark.parametrize("cfg,stride", [(22, 1), (30, 2)])
+def test_stream_k_bits_do_not_depend_on_where_the_workspace_comes_from(dev, cfg, stride):
+    """conv2d's cached stream-K workspace against one the caller made, and the cache growing under a larger map (the buffer it
+    replaces is kept: a captured graph may still point at it): the same bits every time."""
+    B, cin, cout, wgs = 3, 16, 40, 8
+    x, w, xd, pc = _layer(dev, cin, cout, 3, stride, 10, 66, B, 3)
+
+    def own(t):
+        if cfg == 22:
+            return ops.winograd_sk_workspace(B, t.shape[2], t.shape[3], cout, dev, wgs, 0)
+        return ops.conv2d_sk_workspace(B, *pc.tile_hw(t.shape[2], t.shape[3]), cout, 1, dev, wgs)
+
+    run = lambda t, ws=None: ops.conv2d(t, pc, relu=False, tile_cfg=cfg, workspace=ws, workgroups=wgs)
+    first = run(xd)
+    _close(first.cpu(), F.conv2d(x, w, stride=stride, padding=1))
+    assert torch.equal(first, run(xd, own(xd)))
+    x2 = torch.randn(B, cin, 12, 70, generator=torch.Generator().manual_seed(4)).to(dev)
+    assert torch.equal(run(x2), run(x2, own(x2)))
+    assert torch.equal(first, run(xd))
+    # on a stream of its own the cache starts empty: the first map sizes it, a map with more units than its counters hold makes it
+    # grow, and the buffer it had is retired, not freed
+    x3 = torch.randn(B, cin, 96, 132, generator=torch.Generator().manual_seed(5)).to(dev)
+    assert own(x3).numel() > own(xd).numel()
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        a = run(xd)
+        key = [k for k in ops._SK_WS if k[1][0] == side.cuda_stream]
+        assert len(key) == 1
+        old = ops._SK_WS[key[0]]
+        b, c = run(x3), run(xd)
+        assert any(t is old for t in ops._SK_WS_RETIRED) and ops._SK_WS[key[0]].numel() == own(x3).numel()
+        ref3 = run(x3, own(x3))
+    side.synchronize()
+    assert torch.equal(a, first) and torch.equal(c, first) and torch.equal(b, ref3)

@@ -30,9 +30,9 @@ def test_deconv_ks_against_float64(dev, s, cin):
     assert ref.shape == (B, cout, s * H, s * W) and float(ref.max()) > 0 and bool((ref == 0).any())
     pc = ops.pack_deconv2d_ks(w.to(dev), s)
     assert pc.kind == "deconv_ks" and pc.stride == s and len(pc.launches) == s * s
-    assert all(la["ntaps"] == 1 and la["out_mul"] == s and la["in_mul"] == 1 and int(la["dy"][0]) == 0 and int(la["dx"][0]) == 0
+    assert all(la.ntaps == 1 and la.out_mul == s and la.in_mul == 1 and int(la.dy[0]) == 0 and int(la.dx[0]) == 0
                for la in pc.launches)
-    assert sorted((la["py"], la["px"]) for la in pc.launches) == [(py, px) for py in range(s) for px in range(s)]
+    assert sorted((la.py, la.px) for la in pc.launches) == [(py, px) for py in range(s) for px in range(s)]
     out = torch.full((B, cout, s * H, s * W), float("nan"), device=dev)
     got = ops.conv2d(x.to(dev), pc, scale.to(dev), shift.to(dev), True, out=out)
     assert got is out and bool(torch.isfinite(out).all())    # every output pixel belongs to one parity class

@@ -749,6 +749,17 @@ int sessd_deconv2d_s2_pair_split_active(const float* in, int batch, int cin, int
                                         const float* shift_a, const float* scale_b, const float* shift_b, int relu,
                                         const float* residual_a, const float* residual_b, const int32_t* tile_list,
                                         const int32_t* n_list, int list_cap, sessd_stream_t stream);
+/* Conv2d(cin, cout, 3, stride 2, padding 1) + scale / shift / ReLU (+ residual) over a tile list on the bf16 matrix cores at f32
+ * accuracy (csrc/dense_conv_s2_split.hip): the contract of sessd_conv2d_sk_active for that layer -- the four output pixels of
+ * every listed 2x2 tile of the OUTPUT map (entries image * (hout/2 * wout/2) + tile, count on the device, at most list_cap), all
+ * couts; nothing else touched, entries outside the maps ignored, no workspace. wsplit: the (cout, cin, 3, 3) weight as three bf16
+ * planes in the kernel's fragment order, [ceil(cout / 128)][cin / 16][tap 9 = 3 ky + kx][plane 3][cout block 4][lane 64][8]
+ * (ops.pack_conv2d_s2_split). cin % 16 == 0, even hout / wout, hin in {2 hout - 1, 2 hout} and win likewise, the whole batch
+ * inside 32-bit buffer offsets; anything else returns SESSD_EINVAL. One workgroup per (16 list entries, 128 couts), sized from
+ * list_cap; a listed tile's bits do not depend on the rest of the list. */
+int sessd_conv2d_s2_split_active(const float* in, int batch, int cin, int hin, int win, const void* wsplit, float* out, int cout,
+                                 int hout, int wout, const float* scale, const float* shift, int relu, const float* residual,
+                                 const int32_t* tile_list, const int32_t* n_list, int list_cap, sessd_stream_t stream);
 /* rpn_v1.py:227-233: softmax over the two 1-channel weight maps and the weighted sum of x0, x1 */
 int sessd_ssfa_fuse(const float* x0, const float* x1, const float* w0, const float* w1, float bn_scale0,
                     float bn_shift0, float bn_scale1, float bn_shift1, int batch, int channels, int num_pixels,

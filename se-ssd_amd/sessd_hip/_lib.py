@@ -130,6 +130,7 @@ SIGNATURES = {
     "sessd_deconv2d_s2_mfma_pair_active": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp,
                                                  i32, i32, vp]),
     "sessd_deconv2d_s2_pair_split_active": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]),
+    "sessd_conv2d_s2_split_active": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp]),
     "sessd_deconv2d_s2_mfma_pair": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp]),
     "sessd_deconv2d_s2_mfma": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp]),
     "sessd_ssfa_fuse": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, vp, vp]),

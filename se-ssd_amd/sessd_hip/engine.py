@@ -43,6 +43,11 @@ WINO_LIST_SHAPES = (0, 1, 3) if WINO_SPLIT else (0, 1)
 # SESSD_DECONV_SPLIT=0 leaves it out (A/B runs in one tree).
 DECONV_SPLIT = os.environ.get("SESSD_DECONV_SPLIT", "1") != "0"
 PAIR_SPLIT_CFG = 45
+# The stride-2 list layer b1.0 on the bf16 matrix cores (three-way split operands; csrc/dense_conv_s2_split.hip): the active
+# configuration (S2_SPLIT_CFG, 0) beside the LDS-tiled stream-K kernel's (30, min_rounds), among the autotune's candidates.
+# SESSD_CONV_S2_SPLIT=0 leaves it out (A/B runs in one tree).
+CONV_S2_SPLIT = os.environ.get("SESSD_CONV_S2_SPLIT", "1") != "0"
+S2_SPLIT_CFG = 46
 
 SPMIDDLE_LAYERS = [
     ("subm", 4, 16, 3, 1, 0, "subm0"), ("subm", 16, 16, 3, 1, 0, "subm0"),
@@ -465,7 +470,8 @@ class InferenceEngine:
         # computed where its input was) and the rest is filled with the layer's constant.
         # ACTIVE_SLOTS: layer id -> (layer name, layer, input buffer, output buffer); ACTIVE_MASK: id -> slot of the tile mask / list
         # (sessd_bev_tile_activity steps {0, 0, 0, 2, 0, 0, 3, 4, 0}); ACTIVE_SK: ids on the LDS-tiled stream-K kernel (30, min_rounds) or,
-        # for the 1x1 layers, on the direct kernel over the list (tile_cfg, 0); the others: Winograd. Id 8 = the two transposed
+        # for the 1x1 layers, on the direct kernel over the list (tile_cfg, 0), or, for the 3x3 stride-2 layer (id 3), on the split
+        # bf16 list kernel (S2_SPLIT_CFG, 0) -- told from a direct tile_cfg by its number; the others: Winograd. Id 8 = the two transposed
         # convs as one launch over 2x2 tiles of their input (direct kernel, (tile_cfg, 0); buffers: trans_1 in, mid0 / mid1 out).
         self.active_tiles = bool(active_tiles)
         self.active_cfg = {}   # id -> (stream-K shape, min_rounds) / (30, min_rounds), chosen by autotune(); empty = dense launches
@@ -682,7 +688,10 @@ class InferenceEngine:
             # active-tile mode: the listed tiles only (the others were filled with the layer's constant at the head of the stage)
             shape, min_rounds = self.active_cfg[active]
             m = self.ACTIVE_MASK[active]
-            if active in self.ACTIVE_SK and shape != 30:   # a 1x1 layer on the direct kernel over the list
+            if active in self.ACTIVE_SK and shape == S2_SPLIT_CFG:   # the 3x3 stride-2 layer on the split bf16 list kernel
+                call = lambda: ops.conv2d_s2_split_active(x, pc, scale, shift, relu, out, self.ta.tile_list[m], self.ta.n_list[m:m + 1],
+                                                          residual=residual)
+            elif active in self.ACTIVE_SK and shape != 30:   # a 1x1 layer on the direct kernel over the list
                 call = lambda: ops.conv2d_mfma_active(x, pc, scale, shift, relu, out, self.ta.tile_list[m], self.ta.n_list[m:m + 1],
                                                       tile_cfg=shape, residual=residual)
             elif active in self.ACTIVE_SK:
@@ -759,9 +768,11 @@ class InferenceEngine:
             # a Winograd list layer needs its packing for the chosen shape (a missing one is an error, not a fall-back)
             if l == self.ACTIVE_PAIR and shape == PAIR_SPLIT_CFG and any(pc.wsplit() is None for pc, _, _ in self.ACTIVE_SLOTS[l][1]):
                 raise ValueError("active-tile layer %s: no split weight planes (cin %% 16)" % self.ACTIVE_SLOTS[l][0])
+            if shape == S2_SPLIT_CFG and (l not in self.ACTIVE_SK or self.ACTIVE_SLOTS[l][1][0].wsplit_s2() is None):
+                raise ValueError("active-tile layer %s: no split weight planes of a 3x3 stride-2 conv (cin %% 16)" % self.ACTIVE_SLOTS[l][0])
             if l in self.ACTIVE_SK or l == self.ACTIVE_PAIR:
                 continue
-            layers = self.ACTIVE_SLOTS[l][1] if l == self.ACTIVE_CONV else (self.ACTIVE_SLOTS[l][1],)
+            layers =self.ACTIVE_SLOTS[l][1] if l == self.ACTIVE_CONV else (self.ACTIVE_SLOTS[l][1],)
             if any(pc.upk_sk(shape) is None for pc, _, _ in layers):
                 raise ValueError("active-tile layer %s: no stream-K Winograd packing for shape %d" % (self.ACTIVE_SLOTS[l][0], shape))
         self.active_cfg = cfg
@@ -958,6 +969,11 @@ class InferenceEngine:
                                                                 self.ta.n_list[m:m + 1], workgroups=self._wgs(2), min_rounds=mr))
                         if tt < best[1]:
                             best = ((30, mr), tt)
+                if CONV_S2_SPLIT and pc.wsplit_s2() is not None:   # the 3x3 stride-2 layer: whole units on the bf16 matrix cores
+                    tt = timed(lambda: ops.conv2d_s2_split_active(x_in, pc, scale, shift, True, x_out, self.ta.tile_list[m],
+                                                                  self.ta.n_list[m:m + 1]))
+                    if tt < best[1]:
+                        best = ((S2_SPLIT_CFG, 0), tt)
             else:
                 for shape in WINO_LIST_SHAPES:
                     if pc.upk_sk(shape) is None:

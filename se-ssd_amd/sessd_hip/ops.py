@@ -1593,6 +1593,7 @@ class PackedConv:
         self._upk_sk = [None, None, None, None]
         self._sk = None      # argument block of sessd_conv2d_sk (tile_cfg 30), made when first asked for
         self._wsplit = None
+        self._wsplit_s2 = None
         self._registry = None  # RepackRegistry that keeps this object fresh (training step), else None
         for la in launches:
             la._owner = self
@@ -1648,6 +1649,18 @@ class PackedConv:
         if self._wsplit is None:
             self._wsplit = pack_deconv2d_s2_split(self._wt)
         return self._wsplit
+
+    def wsplit_s2(self):
+        """A Conv2d(3, stride 2, padding 1) weight as three bf16 planes for sessd_conv2d_s2_split_active (pack_conv2d_s2_split),
+        made when first asked for; None if the layer is not eligible (not a 3x3 stride-2 conv, cin % 16)."""
+        if self.kind != "conv" or self.stride != 2 or self.launches[0].ntaps != 9 or self.cin % 16:
+            return None
+        w = self.launches[0].view[0]   # the stored (cout, cin, 3, 3) weight
+        if self._registry is not None:   # a training step's weights change under the registry, which has no job for this packing
+            return pack_conv2d_s2_split(w)
+        if self._wsplit_s2 is None:
+            self._wsplit_s2 = pack_conv2d_s2_split(w)
+        return self._wsplit_s2
 
     def sk_args(self):
         """Host-side argument block of sessd_conv2d_sk (tile_cfg 30): the launches' weights re-packed in the kernel's LDS image
@@ -2024,6 +2037,46 @@ def deconv2d_s2_pair_split_active(x, pc_a, pc_b, scale_a, shift_a, scale_b, shif
     check(lib.sessd_deconv2d_s2_pair_split_active(*args, tile_list.data_ptr(), n_list.data_ptr(), tile_list.numel(), _stream()),
           "deconv2d_s2_pair_split_active")
     return out_a, out_b
+
+
+def pack_conv2d_s2_split(weight):
+    """nn.Conv2d(Cin, Cout, 3, stride 2, padding 1) weight (Cout, Cin, 3, 3), Cin % 16 == 0, for sessd_conv2d_s2_split_active:
+    w = w0 + w1 + w2 EXACTLY with three bfloat16 terms (each rounded to nearest from the f32 residual of the one before), stored
+    [ceil(Cout/128)][Cin/16][tap 9 = 3 ky + kx][plane 3][(cout/32)%4][lane = (cin/8)%2 * 32 + cout%32][cin%8] -- a wave's A
+    fragment of a (k-step, tap, plane) is 16 contiguous bytes per lane. Couts beyond Cout are zero. Once per model (plain torch,
+    on the weight's device)."""
+    w = weight.detach().to(torch.float32)
+    if w.dim() != 4 or w.shape[2] != 3 or w.shape[3] != 3 or w.shape[1] % 16:
+        raise ValueError("pack_conv2d_s2_split: a (Cout, Cin, 3, 3) weight with Cin % 16 == 0")
+    co, ci = w.shape[0], w.shape[1]
+    ng = (co + 127) // 128
+    wt = torch.zeros((9, ci, ng * 128), dtype=torch.float32, device=w.device)
+    wt[:, :, :co] = w.permute(2, 3, 1, 0).reshape(9, ci, co)
+    planes = []
+    for _ in range(3):
+        p = wt.to(torch.bfloat16)
+        planes.append(p)
+        wt = wt - p.to(torch.float32)   # exact: the residual of a round-to-nearest bf16 fits f32
+    pl = torch.stack(planes).view(3, 9, ci // 16, 2, 8, ng, 4, 32)   # plane, tap, k-step, cin half, cin % 8, group, cout block, cout % 32
+    return pl.permute(5, 2, 1, 0, 6, 3, 7, 4).contiguous().view(ng, ci // 16, 9, 3, 4, 64, 8)
+
+
+def conv2d_s2_split_active(x, pc, scale, shift, relu, out, tile_list, n_list, residual=None):
+    """sessd_conv2d_s2_split_active: a Conv2d(3, stride 2, padding 1) layer on the bf16 matrix cores (three-way split operands, f32
+    accuracy) over the listed 2x2 tiles of its OUTPUT map (entries image * (ho/2 * wo/2) + tile, count on the device); the other
+    output pixels of `out` are left alone."""
+    _req(x, torch.float32, "x"); _req(out, torch.float32, "out"); _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
+    ws = pc.wsplit_s2()
+    if ws is None:
+        raise ValueError("conv2d_s2_split_active needs a 3x3 stride-2 conv with cin % 16 == 0")
+    B, ci, H, W = x.shape
+    ho, wo = pc.out_hw(H, W)
+    if ci != pc.cin or tuple(out.shape) != (B, pc.cout, ho, wo):
+        raise ValueError("conv2d_s2_split_active: x (B, cin, H, W) and out (B, cout, ceil(H/2), ceil(W/2))")
+    check(lib.sessd_conv2d_s2_split_active(x.data_ptr(), B, ci, H, W, ws.data_ptr(), out.data_ptr(), pc.cout, ho, wo, _p(scale), _p(shift),
+                                           1 if relu else 0, _p(residual), tile_list.data_ptr(), n_list.data_ptr(), tile_list.numel(),
+                                           _stream()), "conv2d_s2_split_active")
+    return out
 
 
 def pack_deconv2d_ks(weight, s):

@@ -12,6 +12,7 @@ it reads their parameters (reference state_dict layout), folds eval-mode BatchNo
 """
 import math
 import os
+from typing import Any, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -63,6 +64,65 @@ SPMIDDLE_LAYERS = [
 
 def _t3(v):
     return [int(v)] * 3 if isinstance(v, int) else [int(x) for x in v]
+
+
+class ListLayer(NamedTuple):
+    """One row of an engine's table of list layers (`InferenceEngine.lists`: id -> row): a dense layer, or two that share a tile
+    list, that can run over the tiles sessd_bev_tile_activity lists instead of the whole map.
+    kind: "wino" = a 3x3 stride-1 layer on the stream-K Winograd list kernel, configuration (shape, min_rounds);
+          "direct" = a stride-2 or 1x1 layer: (30, min_rounds) on the LDS-tiled stream-K kernel, (tile_cfg 3 / 4 / 11 / 12, 0) on the
+                     direct kernel (1x1 only), (S2_SPLIT_CFG, 0) on the split bf16 kernel (3x3 stride 2 only);
+          "pair" = the two transposed convs as one launch over 2x2 tiles of their input: (tile_cfg, 0) or (PAIR_SPLIT_CFG, 0);
+          "branches" = conv_0 and conv_1 over one list, a Winograd list launch each: (shape, min_rounds).
+    layer / x_in / x_out are pairs where the row holds two layers ("pair": one input, two outputs; "branches": two of each)."""
+    name: str
+    layer: Any
+    x_in: Any
+    x_out: Any
+    mask: int              # slot of the row's tile mask / list (sessd_bev_tile_activity)
+    kind: str
+    near: Optional[int]    # id of the map's ONE reader where that is a 3x3 stride-1 layer on the same tile grid, else None
+
+
+# Outputs whose readers run on a grid twice as coarse, or on the map's own list (coarse_fill): name -> (the readers, which must all
+# run over lists; the reader whose list bounds what the fill has to reach, None = nothing needs the constant; near kind).
+#   x0 (b0.2's output): read by b1.0 (3x3 stride 2, a list on the grid of ITS output: kind 2) and by trans_0 (1x1 over x0's own
+#      list: computed tiles only);
+#   tr0 (trans_0's output): read by the transposed pair as a residual inside its listed 4x4-pixel blocks (kind 1);
+#   x1 (b1.2's output): read by trans_1 alone -- when that runs over x1's own list, NOTHING needs the constant (job dropped)
+COARSE_READERS = {"b0.2": (("b1.0", "trans_0"), "b1.0", 2), "trans_0": (("deconv_0+deconv_1",), "deconv_0+deconv_1", 1),
+                  "b1.2": (("trans_1",), None, 0)}
+
+
+def fill_reach(table, ids, near_fill=True, coarse_fill=True):
+    """The jobs of sessd_fill_inactive_tiles for the list layers `ids` of `table` (id -> ListLayer; names, kinds, masks and near
+    ids are all it reads): a list of (id, part, mask slot, tile size, near slot or None, near kind), part = which of a row's two
+    outputs (None: it has one). Which tiles of a map need the layer's constant depends on who reads it (near_fill): a map whose
+    readers all run over tile lists gets it only where they can reach --
+      a map with a `near` reader that runs over its list: 3x3 tiles around that list (kind 0);
+      the maps of COARSE_READERS (coarse_fill): see there;
+    everything a full-map launch reads (trans_1's and the pair's outputs, and any of the above whose reader stayed on the full
+    map) is filled everywhere. Tile sizes: 2 = the layer's 2x2-output tiles; one constant per output parity class behind the
+    transposed pair (4: 4x4 blocks) and behind conv_0 / conv_1 (6: 2x2 tiles)."""
+    ids = list(ids)
+    by_name = {table[l].name: l for l in ids}
+    jobs = []
+    for l in ids:
+        row = table[l]
+        if row.kind in ("pair", "branches"):
+            jobs += [(l, part, row.mask, 4 if row.kind == "pair" else 6, None, 0) for part in (0, 1)]
+            continue
+        nr, kind = None, 0
+        if near_fill:
+            readers, bound, ckind = COARSE_READERS.get(row.name, ((), None, 0))
+            if row.near is not None and row.near in ids and table[row.near].kind == "wino":
+                nr = table[row.near].mask
+            elif coarse_fill and readers and all(r in by_name for r in readers):
+                if bound is None:
+                    continue
+                nr, kind = table[by_name[bound]].mask, ckind
+        jobs.append((l, None, row.mask, 2, nr, kind))
+    return jobs
 
 
 class SparsePlan:
@@ -183,6 +243,29 @@ class DensePlan:
         self.head_w = hw.reshape(hw.shape[0], -1).float().contiguous()  # row-major (T * 22, C): the fused SSFA-tail + heads launch
         self.head_b = hb
 
+    # the program of sessd_bev_tile_activity behind the list layers: masks 0 - 5 = the two blocks (2 = a stride-2 step), 6 = the
+    # transposed pair over trans_1's map, 7 = conv_0 / conv_1 over the pair's output (steps 3, 4)
+    ACTIVITY_STEPS = (0, 0, 0, 2, 0, 0, 3, 4, 0)
+
+    def list_layers(self, bev, t, h):
+        """id -> ListLayer over the engine's buffers (bev, full-resolution t, half-resolution h). Ids 0 - 5: bottom_up_block_0 /
+        bottom_up_block_1; 6 / 7: the 1x1 trans layers over the lists of x0 / x1; 8: the two transposed convs as one launch over
+        2x2 tiles of their input; 9: conv_0 and conv_1 (rpn_v1.py:200-210) over the 2x2 tiles of the transposed convs' OUTPUT that
+        can differ from their per-parity-class constants (two launches, one list)."""
+        rows = [("b0.0", self.b0[0], bev, t["a"], 0, "wino", 1), ("b0.1", self.b0[1], t["a"], t["b"], 1, "wino", 2),
+                ("b0.2", self.b0[2], t["b"], t["x0"], 2, "wino", None), ("b1.0", self.b1[0], t["x0"], h["a"], 3, "direct", 4),
+                ("b1.1", self.b1[1], h["a"], h["b"], 4, "wino", 5), ("b1.2", self.b1[2], h["b"], h["x1"], 5, "wino", None),
+                ("trans_0", self.trans_0, t["x0"], t["tr0"], 2, "direct", None),
+                ("trans_1", self.trans_1, h["x1"], h["tr1"], 5, "direct", None),
+                ("deconv_0+deconv_1", (self.deconv_0, self.deconv_1), h["tr1"], (t["mid0"], t["mid1"]), 6, "pair", None),
+                ("conv_0+conv_1", (self.conv_0, self.conv_1), (t["mid0"], t["mid1"]), (t["o0"], t["o1"]), 7, "branches", None)]
+        return {l: ListLayer(*row) for l, row in enumerate(rows)}
+
+    def default_active_cfg(self):
+        """what autotune() ends in on MI355X; with WINO_SPLIT the 8-wave list layers on the bf16 matrix cores (shape 3)"""
+        s8 = 3 if WINO_SPLIT else 0
+        return {0: (1, 4), 1: (s8, 1), 2: (1, 2), 3: (30, 4), 4: (1, 2), 5: (s8, 1), 6: (11, 0), 7: (30, 8), 8: (4, 0), 9: (s8, 8)}
+
 
 def _const_step(conv, bn, c):
     """relu(scale * (sum_k W[co][ci][k]) @ c + shift): what a conv + BN + ReLU layer computes on the constant map c, float64"""
@@ -265,6 +348,30 @@ class RpnPlan:
         self.head = (ops.pack_conv2d(hw), None, hb)
         self.head_w = hw.reshape(hw.shape[0], -1).float().contiguous()  # row-major (T * 22, C): the fused tail + heads launch
         self.head_b = hb
+
+    @property
+    def ACTIVITY_STEPS(self):
+        """layer i = mask slot i, all stride 1"""
+        return (0,) * len(self.layers)
+
+    def list_layers(self, bev, t, h):
+        """id -> ListLayer, one row per layer of the block, all on the Winograd list launches, where every layer has a map of its
+        own (t["l0"] ...: an engine with a tile-activity program); outputs 0 .. n-2 have one reader each, the next layer on the same
+        grid, the last one is read by the tail launch over the whole map (filled everywhere)."""
+        nl = len(self.layers)
+        if "l%d" % (nl - 1) not in t:
+            return {}
+        bufs = [bev] + [t["l%d" % i] for i in range(nl)]
+        return {i: ListLayer("blk0.%d" % i, self.layers[i], bufs[i], bufs[i + 1], i, "wino", i + 1 if i < nl - 1 else None)
+                for i in range(nl)}
+
+    def default_active_cfg(self):
+        """what autotune() chose on MI355X for the full-size three-class engine (DESIGN.md section 3,
+        profiles/rpn_tail_and_lists.json): the four-wave shape, stream-K shares of >= 4 rounds for the first (shortest) list and
+        whole units for the next three; the eight-wave shape (bf16 split where built) on whole units for the last two"""
+        s8 = 3 if WINO_SPLIT else 0
+        tuned = [(1, 4), (1, -1), (1, -1), (1, -1), (s8, -1), (s8, -1)]
+        return {i: tuned[min(i, 5)] for i in range(len(self.layers))}
 
 
 class InferenceEngine:
@@ -415,6 +522,7 @@ class InferenceEngine:
             if nl > 8:
                 tiles_ok = False   # sessd_bev_tile_activity takes at most eight slots
             self.t = {k: E(B, 128, H, W) for k in ["l%d" % i for i in range(nl if tiles_ok else min(nl, 2))] + ["out"]}
+            self._rpn_bufs = [self.bev] + [self.t["l%d" % (i if tiles_ok else i & 1)] for i in range(nl)]
         else:
             self.t = {k: E(B, 128, H, W) for k in ("a", "b", "x0", "tr0", "out")}
         # the two branches after the transposed convs are one shape: adjacent buffers, so that conv_0 / conv_1 can be one launch
@@ -468,52 +576,22 @@ class InferenceEngine:
         # outside the last sparse level's sites, so these layers are computed only in the 2x2-output tiles whose input patch is
         # not constant (14 / 26 / 36 % of the tiles of block 0, 46 / 54 / 68 % of block 1's on a 20 k-point scan; a 1x1 layer is
         # computed where its input was) and the rest is filled with the layer's constant.
-        # ACTIVE_SLOTS: layer id -> (layer name, layer, input buffer, output buffer); ACTIVE_MASK: id -> slot of the tile mask / list
-        # (sessd_bev_tile_activity steps {0, 0, 0, 2, 0, 0, 3, 4, 0}); ACTIVE_SK: ids on the LDS-tiled stream-K kernel (30, min_rounds) or,
-        # for the 1x1 layers, on the direct kernel over the list (tile_cfg, 0), or, for the 3x3 stride-2 layer (id 3), on the split
-        # bf16 list kernel (S2_SPLIT_CFG, 0) -- told from a direct tile_cfg by its number; the others: Winograd. Id 8 = the two transposed
-        # convs as one launch over 2x2 tiles of their input (direct kernel, (tile_cfg, 0); buffers: trans_1 in, mid0 / mid1 out).
+        # self.lists: id -> ListLayer, the table everything below reads (the plan's list_layers()); the masks are the slots of the
+        # plan's ACTIVITY_STEPS program.
         self.active_tiles = bool(active_tiles)
-        self.active_cfg = {}   # id -> (stream-K shape, min_rounds) / (30, min_rounds), chosen by autotune(); empty = dense launches
-        # The per-form tables below are instance data chosen by the plan's form. An RPN engine: the program of its stride-1 layers is
-        # {0, 0, 0, 0, 0, 0}, layer i = slot i, all on the Winograd list launches; outputs 0 .. n-2 have one reader each, the next
-        # layer on the same grid (near-fill kind 0), the last one is read by the tail launch over the whole map (filled everywhere).
-        ok = tiles_ok
-        if self.form == "rpn":
-            nl = len(self.dn.layers)
-            self.ta = ops.TileActivity(B, H, W, [0] * nl, dev) if ok else None
-            bufs = [self.bev] + [self.t["l%d" % (i if ok else i & 1)] for i in range(nl)]
-            self._rpn_bufs = bufs
-            self.ACTIVE_SLOTS_RPN = {i: ("blk0.%d" % i, self.dn.layers[i], bufs[i], bufs[i + 1]) for i in range(nl)} if ok else {}
-        else:
-            self.ta = ops.TileActivity(B, H, W, [0, 0, 0, 2, 0, 0, 3, 4, 0], dev) if ok else None
-        self.ACTIVE_SLOTS = self.ACTIVE_SLOTS_RPN if self.form == "rpn" else {0: ("b0.0", self.dn.b0[0], self.bev, self.t["a"]), 1: ("b0.1", self.dn.b0[1], self.t["a"], self.t["b"]),
-                             2: ("b0.2", self.dn.b0[2], self.t["b"], self.t["x0"]), 3: ("b1.0", self.dn.b1[0], self.t["x0"], self.h["a"]),
-                             4: ("b1.1", self.dn.b1[1], self.h["a"], self.h["b"]), 5: ("b1.2", self.dn.b1[2], self.h["b"], self.h["x1"]),
-                             6: ("trans_0", self.dn.trans_0, self.t["x0"], self.t["tr0"]),
-                             7: ("trans_1", self.dn.trans_1, self.h["x1"], self.h["tr1"]),
-                             8: ("deconv_0+deconv_1", (self.dn.deconv_0, self.dn.deconv_1), self.h["tr1"], (self.t["mid0"], self.t["mid1"])),
-                             9: ("conv_0+conv_1", (self.dn.conv_0, self.dn.conv_1), (self.t["mid0"], self.t["mid1"]), (self.t["o0"], self.t["o1"]))}
-        self.ACTIVE_MASK = {0: 0, 1: 1, 2: 2, 3: 3, 4: 4, 5: 5, 6: 2, 7: 5, 8: 6, 9: 7}
-        self.ACTIVE_SK = (3, 6, 7)
-        self.ACTIVE_PAIR = 8
-        self.NEAR_READER = type(self).NEAR_READER
-        self.DEFAULT_ACTIVE_CFG = type(self).DEFAULT_ACTIVE_CFG
-        # Id 9 (round 6) = conv_0 and conv_1 (rpn_v1.py:200-210) over the 2x2 tiles of the transposed convs' OUTPUT that can differ from
-        # their per-parity-class constants (step program {.., 3, 4, 0}: 0.69 - 0.85 of the tiles of a 20 k-point scan): two Winograd list
-        # launches (one per branch, one list), the rest of o0 / o1 filled with the (4, cout) parity constants
-        self.ACTIVE_CONV = 9
-        if self.form == "rpn":
-            nl = len(self.dn.layers)
-            self.ACTIVE_MASK = {i: i for i in self.ACTIVE_SLOTS}
-            self.ACTIVE_SK, self.ACTIVE_PAIR, self.ACTIVE_CONV = (), -1, -1   # no stride-2 / 1x1 list layers, no pair, no branches
-            self.NEAR_READER = {i: i + 1 for i in range(nl - 1)}
-            # defaults = what autotune() chose on MI355X for the full-size three-class engine (DESIGN.md section 3,
-            # profiles/rpn_tail_and_lists.json): the four-wave shape, stream-K shares of >= 4 rounds for the first (shortest) list
-            # and whole units for the next three; the eight-wave shape (bf16 split where built) on whole units for the last two
-            s8 = 3 if WINO_SPLIT else 0
-            tuned = [(1, 4), (1, -1), (1, -1), (1, -1), (s8, -1), (s8, -1)]
-            self.DEFAULT_ACTIVE_CFG = {i: tuned[min(i, 5)] for i in self.ACTIVE_SLOTS}
+        self.active_cfg = {}   # id -> (number, min_rounds) as ListLayer.kind reads it, chosen by autotune(); empty = dense launches
+        self.ta = ops.TileActivity(B, H, W, list(self.dn.ACTIVITY_STEPS), dev) if tiles_ok else None
+        self.lists = self.dn.list_layers(self.bev, self.t, self.h)
+        self._list_id = {row.name: l for l, row in self.lists.items()}
+        self._kind_id = {kind: next((l for l, row in self.lists.items() if row.kind == kind), -1) for kind in ("pair", "branches")}
+        # the table as bench.py and the tests read it (nothing in the engine does): the rows (positional reads), mask slots, the
+        # "direct" ids, the id of the pair / of the branches (-1: none), the near readers, the default configuration
+        self.ACTIVE_SLOTS = self.lists
+        self.ACTIVE_MASK = {l: row.mask for l, row in self.lists.items()}
+        self.ACTIVE_SK = tuple(l for l, row in self.lists.items() if row.kind == "direct")
+        self.ACTIVE_PAIR, self.ACTIVE_CONV = self._kind_id["pair"], self._kind_id["branches"]
+        self.NEAR_READER = {l: row.near for l, row in self.lists.items() if row.near is not None}
+        self.DEFAULT_ACTIVE_CFG = {l: c for l, c in self.dn.default_active_cfg().items() if l in self.lists}
         self.allow_active_conv = True   # autotune() may put conv_0 / conv_1 on their tile list (bench.py --no-active-conv: A/B)
         self.near_fill = True   # fill only the tiles a list-driven reader can reach where that reader is the map's only one
         self.coarse_fill = True  # ... also where the readers run on a grid twice as coarse (x0, tr0) or on the map's own list (x1): round 5
@@ -635,91 +713,163 @@ class InferenceEngine:
                                     shift=torch.stack([t0, t1]).contiguous()) if ok else None)
         return getattr(self, key)
 
-    # a map with ONE reader, a 3x3 stride-1 layer on the same tile grid: id -> id of that reader. When the reader runs over its
-    # list, only the tiles it can reach need the constant (sessd_fill_tiles_job_t.near_mask)
-    NEAR_READER = {0: 1, 1: 2, 3: 4, 4: 5}
-
     def _fill_jobs(self, ids):
-        """(outs, values, mask slots, tile sizes, near slots, near kinds) of sessd_fill_inactive_tiles for the active layer ids.
-        Which tiles of a map need the constant depends on who reads it (near_fill): a map whose readers all run over tile lists
-        gets it only where they can reach --
-          b0.0 / b0.1 / b1.0 / b1.1 outputs: one reader, the next 3x3 stride-1 layer on the same grid (kind 0: 3x3 tiles around its list);
-          x0 (b0.2's output): read by b1.0 (3x3 stride 2, a list on the grid of ITS output: kind 2) and by trans_0 (1x1 over x0's own
-             list: computed tiles only);
-          x1 (b1.2's output): read by trans_1 alone -- when that runs over x1's own list, NOTHING needs the constant (job dropped);
-          tr0 (trans_0's output): read by the transposed pair as a residual inside its listed 4x4-pixel blocks (kind 1);
-        everything a full-map launch reads (trans_1's and the pair's outputs, and any of the above whose reader stayed on the full
-        map) is filled everywhere."""
-        outs, vals, slots, tiles, near, kinds = [], [], [], [], [], []
-        ids = list(ids)
-        for l in ids:
-            if l in (self.ACTIVE_PAIR, self.ACTIVE_CONV):
-                # one constant per output parity class: 4x4 blocks behind the transposed pair, 2x2 tiles behind conv_0 / conv_1
-                for o, v in zip(self.ACTIVE_SLOTS[l][3], self.dn.act_const[l]):
-                    outs.append(o); vals.append(v); slots.append(self.ACTIVE_MASK[l]); tiles.append(4 if l == self.ACTIVE_PAIR else 6)
-                    near.append(None); kinds.append(0)
-                continue
-            nr, kind = None, 0
-            if self.near_fill:
-                rd = self.NEAR_READER.get(l)
-                if rd is not None and rd in ids and rd not in self.ACTIVE_SK:
-                    nr = self.ACTIVE_MASK[rd]
-                elif self.form != "ssfa":
-                    pass
-                elif self.coarse_fill and l == 2 and 3 in ids and 6 in ids:
-                    nr, kind = self.ACTIVE_MASK[3], 2
-                elif self.coarse_fill and l == 6 and self.ACTIVE_PAIR in ids:
-                    nr, kind = self.ACTIVE_MASK[self.ACTIVE_PAIR], 1
-                elif self.coarse_fill and l == 5 and 7 in ids:
-                    continue   # x1's only reader walks x1's own list
-            outs.append(self.ACTIVE_SLOTS[l][3]); vals.append(self.dn.act_const[l]); slots.append(self.ACTIVE_MASK[l]); tiles.append(2)
-            near.append(nr); kinds.append(kind)
+        """(outs, values, mask slots, tile sizes, near slots, near kinds) of sessd_fill_inactive_tiles for the active layer ids:
+        fill_reach()'s jobs with their buffers and constants."""
+        jobs = fill_reach(self.lists, ids, self.near_fill, self.coarse_fill)
+        pick = lambda v, part: v if part is None else v[part]
+        outs = [pick(self.lists[l].x_out, part) for l, part, *_ in jobs]
+        vals = [pick(self.dn.act_const[l], part) for l, part, *_ in jobs]
+        slots, tiles, near, kinds = ([j[i] for j in jobs] for i in (2, 3, 4, 5))
         return outs, vals, slots, tiles, near, kinds
 
-    def _active_layers(self):
-        """slots (ACTIVE_SLOTS) of the layers that run in active-tile mode in this configuration"""
-        if self.ta is None or self._tuning is not None or self.sk_ws is None:
-            return []
-        return sorted(self.active_cfg)
+    def _lists_on(self):
+        return self.ta is not None and self._tuning is None and self.sk_ws is not None
 
-    def _conv(self, x, layer, out, relu=True, residual=None, name=None, active=None):
+    def _active_layers(self):
+        """ids (self.lists) of the layers that run in active-tile mode in this configuration"""
+        return sorted(self.active_cfg) if self._lists_on() else []
+
+    def _bracket(self, name, fn):
+        """fn(), between two HIP events kept under `name` when a frame collects per-launch times (dense_layer_times)"""
+        if self._kmarks is None:
+            return fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        r = fn()
+        e1.record()
+        self._kmarks.append((name, e0, e1))
+        return r
+
+    def _time(self, fn, reps):
+        """ms per fn() on the current stream: two warm-up calls, then `reps` calls between two HIP events; synchronises"""
+        for _ in range(2):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    # ------------------------------------------------------------------ the list layers: what a configuration means, per kind
+    def _list_parts(self, l):
+        """[(layer, input, output)] of row l: one per launch of a "wino" / "branches" row"""
+        row = self.lists[l]
+        return list(zip(row.layer, row.x_in, row.x_out)) if row.kind == "branches" else [(row.layer, row.x_in, row.x_out)]
+
+    def _list_cfg_error(self, l, cfg):
+        """None, or why list layer l cannot run under cfg = (number, min_rounds): a missing packing is an error, not a fall-back"""
+        if l not in self.lists:
+            return "an %s engine's list layers are %s, got %r" % (self.form.upper(), sorted(self.lists), l)
+        row, shape = self.lists[l], cfg[0]
+        if row.kind == "pair" and shape == PAIR_SPLIT_CFG and any(pc.wsplit() is None for pc, _, _ in row.layer):
+            return "active-tile layer %s: no split weight planes (cin %% 16)" % row.name
+        if shape == S2_SPLIT_CFG and (row.kind != "direct" or row.layer[0].wsplit_s2() is None):
+            return "active-tile layer %s: no split weight planes of a 3x3 stride-2 conv (cin %% 16)" % row.name
+        if row.kind == "direct" and shape == 30 and row.layer[0].sk_args() is None:
+            return "active-tile layer %s: no LDS-tiled stream-K packing (cin %% 16)" % row.name
+        if row.kind in ("wino", "branches") and (shape not in (0, 1, 2, 3) or any(pc.upk_sk(shape) is None for (pc, _, _), _, _ in self._list_parts(l))):
+            return "active-tile layer %s: no stream-K Winograd packing for shape %d" % (row.name, shape)
+        return None
+
+    def _list_candidates(self, l):
+        """The configurations autotune() times for list layer l, in the order it tries them (a tie goes to the first)."""
+        row = self.lists[l]
+        if row.kind in ("wino", "branches"):
+            shares = self.list_share_candidates if row.kind == "wino" else (4, 8, 16, -1)
+            for shape in WINO_LIST_SHAPES:
+                if all(pc.upk_sk(shape) is not None for (pc, _, _), _, _ in self._list_parts(l)):
+                    for mr in shares:
+                        yield (shape, mr)
+            return
+        direct = [(cfg, 0) for cfg in (3, 4, 11, 12)]
+        if row.kind == "pair":
+            yield from direct
+            if DECONV_SPLIT and all(pc.wsplit() is not None for pc, _, _ in row.layer):
+                yield (PAIR_SPLIT_CFG, 0)
+            return
+        pc = row.layer[0]
+        if pc.launches[0].ntaps == 1 and pc.cin % 8 == 0:
+            yield from direct
+        if pc.sk_args() is not None:
+            for mr in (1, 4, 8, 16):
+                yield (30, mr)
+        if CONV_S2_SPLIT and pc.wsplit_s2() is not None:   # the 3x3 stride-2 layer: whole units on the bf16 matrix cores
+            yield (S2_SPLIT_CFG, 0)
+
+    def _list_ws_bytes(self, l, cfg):
+        """stream-K workspace the launch of _list_call(l, cfg) needs (0: it uses none)"""
+        row, shape = self.lists[l], cfg[0]
+        if row.kind == "pair" or (row.kind == "direct" and shape != 30):
+            return 0
+        (pc, _, _), x_in, _ = self._list_parts(l)[0]
+        if row.kind == "direct":
+            return int(lib.sessd_conv2d_sk_workspace_bytes(self.B, *pc.tile_hw(*x_in.shape[2:]), pc.cout, len(pc.launches), 0))
+        return int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(self.B, x_in.shape[2], x_in.shape[3], pc.cout, shape, 0))
+
+    def _list_call(self, l, cfg):
+        """A callable that issues the launch (the two launches of "branches") of list layer l under cfg = (number, min_rounds) over
+        the listed tiles only: the others hold the layer's constant from the fill at the head of the stage."""
+        err = self._list_cfg_error(l, cfg)
+        if err is not None:
+            raise ValueError(err)
+        row, (shape, mr) = self.lists[l], cfg
+        lst = lambda: (self.ta.tile_list[row.mask], self.ta.n_list[row.mask:row.mask + 1])
+        if row.kind in ("wino", "branches"):
+            parts = self._list_parts(l)
+            def call():
+                for (pc, scale, shift), x, out in parts:
+                    ops.conv2d_winograd_sk_active(x, pc.upk_sk(shape), pc.cout, scale, shift, True, out, shape, self.sk_ws, *lst(),
+                                                  workgroups=self._wgs(shape), min_rounds=mr)
+            return call
+        if row.kind == "pair":   # both transposed convs; trans_0's map is deconv_0's residual
+            (pa, sa, ta), (pb, sb, tb) = row.layer
+            args = (row.x_in, pa, pb, sa, ta, sb, tb, True, row.x_out[0], row.x_out[1])
+            if shape == PAIR_SPLIT_CFG:
+                return lambda: ops.deconv2d_s2_pair_split_active(*args, *lst(), residual_a=self.t["tr0"])
+            return lambda: ops.deconv2d_s2_pair_active(*args, *lst(), residual_a=self.t["tr0"], tile_cfg=shape)
+        pc, scale, shift = row.layer
+        if shape == S2_SPLIT_CFG:   # the 3x3 stride-2 layer on the split bf16 list kernel
+            return lambda: ops.conv2d_s2_split_active(row.x_in, pc, scale, shift, True, row.x_out, *lst())
+        if shape == 30:
+            return lambda: ops.conv2d_sk_active(row.x_in, pc, scale, shift, True, row.x_out, self.sk_ws, *lst(), workgroups=self._wgs(2),
+                                                min_rounds=mr)
+        return lambda: ops.conv2d_mfma_active(row.x_in, pc, scale, shift, True, row.x_out, *lst(), tile_cfg=shape)   # a 1x1 layer
+
+    def _full_map_pair(self):
+        """Both transposed convs read tr1: ONE launch over their 2 x 4 parity classes (same bits as two launches) where both were
+        tuned to a direct tile_cfg; None = the two layers' own launches."""
+        cd = self.tile_cfg.get("deconv_0")
+        if not (self.merge_branch_convs and cd in (3, 4, 11, 12) and self.tile_cfg.get("deconv_1") in (3, 4, 11, 12) and self._tuning is None):
+            return None
+        d, t = self.dn, self.t
+        (pa, sa, ta), (pb, sb, tb) = d.deconv_0, d.deconv_1
+        return lambda: ops.deconv2d_s2_pair(self.h["tr1"], pa, pb, sa, ta, sb, tb, True, t["mid0"], t["mid1"], residual_a=t["tr0"], tile_cfg=cd)
+
+    def _full_map_branches(self):
+        """conv_0 + conv_1 as ONE two-set stream-K Winograd launch where both were tuned to the same stream-K shape; None = the two
+        layers' own launches."""
+        c01 = self.tile_cfg.get("conv_0")
+        if not (self.merge_branch_convs and c01 in (22, 23, 24, 25) and self.tile_cfg.get("conv_1") == c01 and self._tuning is None
+                and self.sk_ws is not None and self._branch_sets(c01 - 22) is not None):
+            return None
+        sets, t = self._branch_sets(c01 - 22), self.t
+        return lambda: ops.conv2d_winograd_sk_sets(t["mid"], sets["upk"], 2, 128, sets["scale"], sets["shift"], True, t["o"], c01 - 22,
+                                                   self.sk_ws, self._wgs(c01 - 22))
+
+    def _conv(self, x, layer, out, relu=True, residual=None, name=None):
+        l = self._list_id.get(name)
+        if l in self.active_cfg and self._lists_on():   # over its tile list (x, out = the row's buffers)
+            self._bracket(name, self._list_call(l, self.active_cfg[l]))
+            return out
         pc, scale, shift = layer
-        if active is not None:
-            # active-tile mode: the listed tiles only (the others were filled with the layer's constant at the head of the stage)
-            shape, min_rounds = self.active_cfg[active]
-            m = self.ACTIVE_MASK[active]
-            if active in self.ACTIVE_SK and shape == S2_SPLIT_CFG:   # the 3x3 stride-2 layer on the split bf16 list kernel
-                call = lambda: ops.conv2d_s2_split_active(x, pc, scale, shift, relu, out, self.ta.tile_list[m], self.ta.n_list[m:m + 1],
-                                                          residual=residual)
-            elif active in self.ACTIVE_SK and shape != 30:   # a 1x1 layer on the direct kernel over the list
-                call = lambda: ops.conv2d_mfma_active(x, pc, scale, shift, relu, out, self.ta.tile_list[m], self.ta.n_list[m:m + 1],
-                                                      tile_cfg=shape, residual=residual)
-            elif active in self.ACTIVE_SK:
-                call = lambda: ops.conv2d_sk_active(x, pc, scale, shift, relu, out, self.sk_ws, self.ta.tile_list[m],
-                                                    self.ta.n_list[m:m + 1], workgroups=self._wgs(2), residual=residual,
-                                                    min_rounds=min_rounds)
-            else:
-                call = lambda: ops.conv2d_winograd_sk_active(x, pc.upk_sk(shape), pc.cout, scale, shift, relu, out, shape, self.sk_ws,
-                                                             self.ta.tile_list[m], self.ta.n_list[m:m + 1],
-                                                             workgroups=self._wgs(shape), residual=residual, min_rounds=min_rounds)
-            if self._kmarks is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                r = call()
-                e1.record()
-                self._kmarks.append((name, e0, e1))
-                return r
-            return call()
         if self._tuning is not None:
             self._tuning.append((name, x, layer, out, relu, residual))
-        if self._kmarks is not None:  # per-launch HIP events inside a whole eager frame (dense_layer_times)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            r = ops.conv2d(x, pc, scale, shift, relu, residual, out, self.tile_cfg.get(name), workspace=self.sk_ws, workgroups=self._wgs_cfg(self.tile_cfg.get(name)))
-            e1.record()
-            self._kmarks.append((name, e0, e1))
-            return r
-        return ops.conv2d(x, pc, scale, shift, relu, residual, out, self.tile_cfg.get(name), workspace=self.sk_ws, workgroups=self._wgs_cfg(self.tile_cfg.get(name)))
+        cfg = self.tile_cfg.get(name)   # per-launch HIP events inside a whole eager frame: dense_layer_times
+        return self._bracket(name, lambda: ops.conv2d(x, pc, scale, shift, relu, residual, out, cfg, workspace=self.sk_ws,
+                                                      workgroups=self._wgs_cfg(cfg)))
 
     def adopt_tuning(self, other):
         """Take another engine's tuned configuration (per-layer tilings, sparse variants, stream-K workgroup count) with a
@@ -733,48 +883,29 @@ class InferenceEngine:
         self.merge_branch_convs = other.merge_branch_convs
         self.sk_ws = torch.zeros_like(other.sk_ws) if other.sk_ws is not None else None
 
-    DEFAULT_ACTIVE_CFG = {0: (1, 4), 1: (0, 1), 2: (1, 2), 3: (30, 4), 4: (1, 2), 5: (0, 1), 6: (11, 0), 7: (30, 8), 8: (4, 0), 9: (0, 8)}
-    if WINO_SPLIT:   # the 8-wave list layers on the bf16 matrix cores (shape 3)
-        DEFAULT_ACTIVE_CFG = {l: ((3, mr) if shape == 0 else (shape, mr)) for l, (shape, mr) in DEFAULT_ACTIVE_CFG.items()}
-
     def force_active_tiles(self, active_cfg=None):
         """The configuration autotune() ends in on MI355X, WITHOUT timing anything: the neck's 3x3 stride-1 layers on the stream-K
-        Winograd kernels, the stride-2 / 1x1 layers on the LDS-tiled stream-K kernel, and every layer of ACTIVE_SLOTS over its
-        tile list with the given (kernel, minimum share) choices (default: all ten). Allocates the stream-K workspace. Used by
-        __graft_entry__.smoke() and the tests, so that what the driver smokes is the kind of configuration bench.py times.
-        An RPN engine: its 3x3 layers over their lists with its own DEFAULT_ACTIVE_CFG (the choice measured on MI355X)."""
+        Winograd kernels, the stride-2 / 1x1 layers on the LDS-tiled stream-K kernel, and every layer of self.lists over its
+        tile list with the given (kernel, minimum share) choices (default: the plan's default_active_cfg(), all of them). Allocates
+        the stream-K workspace. Used by __graft_entry__.smoke() and the tests, so that what the driver smokes is the kind of
+        configuration bench.py times."""
         if self.ta is None:
             raise RuntimeError("this engine has no tile-activity program (active_tiles=False or an unsupported BEV size)")
+        B, wino_ws = self.B, lib.sessd_conv3x3_winograd_sk_workspace_bytes
         if self.form == "rpn":
-            # an RPN engine: its 3x3 layers on the stream-K Winograd kernel (8 waves x 128 couts, exact f32) where they run as
-            # full-map launches, and every layer over its tile list with the given (shape, minimum share) choices
+            # its 3x3 layers on the stream-K Winograd kernel (8 waves x 128 couts, exact f32) where they run as full-map launches
             self.tile_cfg.update({"blk0.%d" % i: 22 for i in range(len(self.dn.layers))})
-            self._need_sk_ws(max(int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(self.B, self.H, self.W, 128, sh, 0)) for sh in (0, 1)))
-            cfg = dict(self.DEFAULT_ACTIVE_CFG if active_cfg is None else active_cfg)
-            for l, (shape, mr) in cfg.items():
-                if l not in self.ACTIVE_SLOTS:
-                    raise ValueError("an RPN engine's list layers are %s, got %r" % (sorted(self.ACTIVE_SLOTS), l))
-                if self.ACTIVE_SLOTS[l][1][0].upk_sk(shape) is None:
-                    raise ValueError("active-tile layer %s: no stream-K Winograd packing for shape %d" % (self.ACTIVE_SLOTS[l][0], shape))
-            self.active_cfg = cfg
-            return self.active_cfg
-        self.tile_cfg.update({"b0.0": 22, "b0.1": 22, "b0.2": 23, "b1.0": 30, "b1.1": 23, "b1.2": 22, "trans_0": 30, "trans_1": 30,
-                              "conv_0": 22, "conv_1": 22})
-        B = self.B
-        self._need_sk_ws(max([int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(2 * B, self.H, self.W, 256, sh, 0)) for sh in (0, 1)] +
-                             [int(lib.sessd_conv2d_sk_workspace_bytes(B, self.H, self.W, 256, 1, 0))]))
-        cfg = dict(self.DEFAULT_ACTIVE_CFG if active_cfg is None else active_cfg)
-        for l, (shape, mr) in cfg.items():
-            # a Winograd list layer needs its packing for the chosen shape (a missing one is an error, not a fall-back)
-            if l == self.ACTIVE_PAIR and shape == PAIR_SPLIT_CFG and any(pc.wsplit() is None for pc, _, _ in self.ACTIVE_SLOTS[l][1]):
-                raise ValueError("active-tile layer %s: no split weight planes (cin %% 16)" % self.ACTIVE_SLOTS[l][0])
-            if shape == S2_SPLIT_CFG and (l not in self.ACTIVE_SK or self.ACTIVE_SLOTS[l][1][0].wsplit_s2() is None):
-                raise ValueError("active-tile layer %s: no split weight planes of a 3x3 stride-2 conv (cin %% 16)" % self.ACTIVE_SLOTS[l][0])
-            if l in self.ACTIVE_SK or l == self.ACTIVE_PAIR:
-                continue
-            layers =self.ACTIVE_SLOTS[l][1] if l == self.ACTIVE_CONV else (self.ACTIVE_SLOTS[l][1],)
-            if any(pc.upk_sk(shape) is None for pc, _, _ in layers):
-                raise ValueError("active-tile layer %s: no stream-K Winograd packing for shape %d" % (self.ACTIVE_SLOTS[l][0], shape))
+            self._need_sk_ws(max(int(wino_ws(B, self.H, self.W, 128, sh, 0)) for sh in (0, 1)))
+        else:
+            self.tile_cfg.update({"b0.0": 22, "b0.1": 22, "b0.2": 23, "b1.0": 30, "b1.1": 23, "b1.2": 22, "trans_0": 30, "trans_1": 30,
+                                  "conv_0": 22, "conv_1": 22})
+            self._need_sk_ws(max([int(wino_ws(2 * B, self.H, self.W, 256, sh, 0)) for sh in (0, 1)] +
+                                 [int(lib.sessd_conv2d_sk_workspace_bytes(B, self.H, self.W, 256, 1, 0))]))
+        cfg = dict(self.dn.default_active_cfg() if active_cfg is None else active_cfg)
+        for l, c in cfg.items():
+            err = self._list_cfg_error(l, c)
+            if err is not None:
+                raise ValueError(err)
         self.active_cfg = cfg
         return self.active_cfg
 
@@ -804,15 +935,7 @@ class InferenceEngine:
                 for srt in ((True, False) if self.chain.sort_tiles else (False,)):
                     self.sparse_split[idx] = split + 256 * depth + 65536 * ks
                     self.sparse_sorted[idx] = srt
-                    for _ in range(2):
-                        self._sconv(lay, in_feat, nbr, tm, out_li, out_feat, st, idx=idx)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(reps):
-                        self._sconv(lay, in_feat, nbr, tm, out_li, out_feat, st, idx=idx)
-                    e1.record()
-                    torch.cuda.synchronize()
-                    t = e0.elapsed_time(e1) / reps
+                    t = self._time(lambda: self._sconv(lay, in_feat, nbr, tm, out_li, out_feat, st, idx=idx), reps)
                     if t < best[1]:
                         best = (split + 256 * depth + 65536 * ks + (1 << 24 if srt else 0), t)
             self.sparse_split[idx] = best[0] & 0xFFFFFF
@@ -855,15 +978,8 @@ class InferenceEngine:
                     continue
                 if cfg == 13 and pc.kind != "conv":
                     continue
-                for _ in range(2):
-                    ops.conv2d(x, pc, scale, shift, relu, residual, out, cfg, workspace=self.sk_ws, workgroups=self._wgs_cfg(cfg))
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(reps):
-                    ops.conv2d(x, pc, scale, shift, relu, residual, out, cfg, workspace=self.sk_ws, workgroups=self._wgs_cfg(cfg))
-                e1.record()
-                torch.cuda.synchronize()
-                t = e0.elapsed_time(e1) / reps
+                t = self._time(lambda: ops.conv2d(x, pc, scale, shift, relu, residual, out, cfg, workspace=self.sk_ws,
+                                                  workgroups=self._wgs_cfg(cfg)), reps)
                 if t < best[1]:
                     best = (cfg, t)
             self.tile_cfg[name] = best[0]
@@ -881,143 +997,55 @@ class InferenceEngine:
         self.active_cfg = {}
         if self.ta is None or not self.allow_streamk or not self.allow_winograd:
             return
-        def timed(fn, n=reps):
-            for _ in range(2):
-                fn()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(n):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            return e0.elapsed_time(e1) / n
-        L4, d = self.levels[-1], self.dn
+        L4 = self.levels[-1]
         self.ta.run(L4["indices"], L4["n"], L4["cap"])
-        pick, gain, pair_dense_t, special_dense = {}, 0.0, 0.0, {}
-        t = self.t
-        for l, (name, layer, x_in, x_out) in self.ACTIVE_SLOTS.items():
+        pick, gain, dense = {}, 0.0, {}
+        full_map = {"pair": self._full_map_pair, "branches": self._full_map_branches}
+        for l, row in self.lists.items():
+            if row.kind == "branches" and not self.allow_active_conv:
+                continue
+            # what enqueue() runs otherwise: the merged launch of two layers (timed here), or each layer's own (timed by autotune())
+            full = full_map[row.kind]() if row.kind in full_map else None
+            dense[l] = self._time(full, reps) if full is not None else sum(self.tune_report.get(n, (None, 0.0))[1] for n in row.name.split("+"))
             best = (None, 1e30)
-            m = self.ACTIVE_MASK[l]
-            if l == self.ACTIVE_PAIR:
-                # the two transposed convs as one launch: over the list against the whole map, both on the direct kernel
-                (pa, sa, ta_), (pb, sb, tb_) = layer
-                tr0 = t["tr0"]
-                cd0, cd1 = self.tile_cfg.get("deconv_0"), self.tile_cfg.get("deconv_1")
-                if self.merge_branch_convs and cd0 in (3, 4, 11, 12) and cd1 in (3, 4, 11, 12):   # what enqueue() runs otherwise
-                    dense_t = timed(lambda: ops.deconv2d_s2_pair(x_in, pa, pb, sa, ta_, sb, tb_, True, x_out[0], x_out[1], residual_a=tr0,
-                                                                 tile_cfg=cd0))
-                else:
-                    dense_t = self.tune_report.get("deconv_0", (None, 0.0))[1] + self.tune_report.get("deconv_1", (None, 0.0))[1]
-                for cfg in (3, 4, 11, 12):
-                    tt = timed(lambda: ops.deconv2d_s2_pair_active(x_in, pa, pb, sa, ta_, sb, tb_, True, x_out[0], x_out[1],
-                                                                   self.ta.tile_list[m], self.ta.n_list[m:m + 1], residual_a=tr0,
-                                                                   tile_cfg=cfg))
-                    if tt < best[1]:
-                        best = ((cfg, 0), tt)
-                if DECONV_SPLIT and pa.wsplit() is not None and pb.wsplit() is not None:
-                    tt = timed(lambda: ops.deconv2d_s2_pair_split_active(x_in, pa, pb, sa, ta_, sb, tb_, True, x_out[0], x_out[1],
-                                                                         self.ta.tile_list[m], self.ta.n_list[m:m + 1], residual_a=tr0))
-                    if tt < best[1]:
-                        best = ((PAIR_SPLIT_CFG, 0), tt)
-                pair_dense_t = dense_t
-                if best[1] < dense_t:
-                    pick[l] = best
-                    gain += dense_t - best[1]
-                continue
-            if l == self.ACTIVE_CONV and not self.allow_active_conv:
-                continue
-            if l == self.ACTIVE_CONV:
-                # conv_0 / conv_1 over ONE list (two launches) against what enqueue() runs otherwise: the two-set full-map launch, or
-                # the two layers' own launches
-                (p0, s0, t0_), (p1, s1, t1_) = layer
-                c01 = self.tile_cfg.get("conv_0")
-                if self.merge_branch_convs and c01 in (22, 23, 24, 25) and self.tile_cfg.get("conv_1") == c01 and self._branch_sets(c01 - 22) is not None:
-                    sets = self._branch_sets(c01 - 22)
-                    dense_t = timed(lambda: ops.conv2d_winograd_sk_sets(t["mid"], sets["upk"], 2, 128, sets["scale"], sets["shift"], True, t["o"],
-                                                                        c01 - 22, self.sk_ws, self._wgs(c01 - 22)))
-                else:
-                    dense_t = self.tune_report.get("conv_0", (None, 0.0))[1] + self.tune_report.get("conv_1", (None, 0.0))[1]
-                for shape in WINO_LIST_SHAPES:
-                    if p0.upk_sk(shape) is None or p1.upk_sk(shape) is None:
-                        continue
-                    self._need_sk_ws(int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(self.B, self.H, self.W, p0.cout, shape, 0)))
-                    for mr in (4, 8, 16, -1):
-                        def both(shape=shape, mr=mr):
-                            for (pc_, sc_, sh_), xi, xo in ((layer[0], x_in[0], x_out[0]), (layer[1], x_in[1], x_out[1])):
-                                ops.conv2d_winograd_sk_active(xi, pc_.upk_sk(shape), pc_.cout, sc_, sh_, True, xo, shape, self.sk_ws,
-                                                              self.ta.tile_list[m], self.ta.n_list[m:m + 1], workgroups=self._wgs(shape), min_rounds=mr)
-                        tt = timed(both)
-                        if tt < best[1]:
-                            best = ((shape, mr), tt)
-                special_dense[l] = dense_t
-                if best[0] is not None and best[1] < dense_t:
-                    pick[l] = best
-                    gain += dense_t - best[1]
-                continue
-            pc, scale, shift = layer
-            if l in self.ACTIVE_SK:
-                if pc.launches[0].ntaps == 1 and pc.cin % 8 == 0:
-                    for cfg in (3, 4, 11, 12):
-                        tt = timed(lambda: ops.conv2d_mfma_active(x_in, pc, scale, shift, True, x_out, self.ta.tile_list[m],
-                                                                  self.ta.n_list[m:m + 1], tile_cfg=cfg))
-                        if tt < best[1]:
-                            best = ((cfg, 0), tt)
-                if pc.sk_args() is not None:
-                    self._need_sk_ws(int(lib.sessd_conv2d_sk_workspace_bytes(self.B, *pc.tile_hw(*x_in.shape[2:]), pc.cout, len(pc.launches), 0)))
-                    for mr in (1, 4, 8, 16):
-                        tt = timed(lambda: ops.conv2d_sk_active(x_in, pc, scale, shift, True, x_out, self.sk_ws, self.ta.tile_list[m],
-                                                                self.ta.n_list[m:m + 1], workgroups=self._wgs(2), min_rounds=mr))
-                        if tt < best[1]:
-                            best = ((30, mr), tt)
-                if CONV_S2_SPLIT and pc.wsplit_s2() is not None:   # the 3x3 stride-2 layer: whole units on the bf16 matrix cores
-                    tt = timed(lambda: ops.conv2d_s2_split_active(x_in, pc, scale, shift, True, x_out, self.ta.tile_list[m],
-                                                                  self.ta.n_list[m:m + 1]))
-                    if tt < best[1]:
-                        best = ((S2_SPLIT_CFG, 0), tt)
-            else:
-                for shape in WINO_LIST_SHAPES:
-                    if pc.upk_sk(shape) is None:
-                        continue
-                    self._need_sk_ws(int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(self.B, x_in.shape[2], x_in.shape[3], pc.cout, shape, 0)))
-                    for mr in self.list_share_candidates:
-                        tt = timed(lambda: ops.conv2d_winograd_sk_active(x_in, pc.upk_sk(shape), pc.cout, scale, shift, True, x_out, shape,
-                                                                         self.sk_ws, self.ta.tile_list[m], self.ta.n_list[m:m + 1],
-                                                                         workgroups=self._wgs(shape), min_rounds=mr))
-                        if tt < best[1]:
-                            best = ((shape, mr), tt)
-            dense_t = self.tune_report.get(name, (None, 0.0))[1]
-            if best[0] is not None and best[1] < dense_t:
+            for cfg in self._list_candidates(l):
+                need = self._list_ws_bytes(l, cfg)
+                if need:
+                    self._need_sk_ws(need)
+                tt = self._time(self._list_call(l, cfg), reps)
+                if tt < best[1]:
+                    best = (cfg, tt)
+            if best[0] is not None and best[1] < dense[l]:
                 pick[l] = best
-                gain += dense_t - best[1]
+                gain += dense[l] - best[1]
         def overhead(ids):
             fj = self._fill_jobs(ids)
-            return timed(lambda: (self.ta.run(L4["indices"], L4["n"], L4["cap"]), self.ta.fill(fj[0], fj[1], layers=fj[2], tiles=fj[3], near=fj[4], near_kind=fj[5])),
-                         4 * reps)   # (differences of a few microseconds are decided on these)
+            return self._time(lambda: (self.ta.run(L4["indices"], L4["n"], L4["cap"]), self.ta.fill(fj[0], fj[1], layers=fj[2], tiles=fj[3], near=fj[4], near_kind=fj[5])),
+                              4 * reps)   # (differences of a few microseconds are decided on these)
         sl = sorted(pick)
         over = overhead(sl) if pick else 0.0
         # the layers whose outputs are read by full-map launches need the constant EVERYWHERE outside their lists (trans_0 / trans_1:
         # 0.4 - 0.7 of an 18 / 9 MB map, the transposed pair: two 18 MB maps): each must pay for its own share of the fill launch
-        for l in (self.ACTIVE_CONV, self.ACTIVE_PAIR, 7, 6):
+        for l in (self._kind_id["branches"], self._kind_id["pair"], 7, 6):
             if l in pick and len(pick) > 1:
                 rest = [q for q in sl if q != l]
                 over_wo = overhead(rest)
-                g = (special_dense[l] if l in special_dense else
-                     self.tune_report.get(self.ACTIVE_SLOTS[l][0], (None, 0.0))[1] if l != self.ACTIVE_PAIR else pair_dense_t) - pick[l][1]
+                g = dense[l] - pick[l][1]
                 if over - over_wo >= g:
                     del pick[l]
                     sl, over, gain = rest, over_wo, gain - g
         if pick and gain > over:
             self.active_cfg = {l: pick[l][0] for l in pick}
         # (choice, gain ms per frame over the dense launches, ms of the activity + fill launches, per-layer ms): a tuple like the others
-        self.tune_report["active_tiles"] = ({self.ACTIVE_SLOTS[l][0]: v for l, v in self.active_cfg.items()}, gain - over, over,
-                                            {self.ACTIVE_SLOTS[l][0]: pick[l][1] for l in pick})
+        self.tune_report["active_tiles"] = ({self.lists[l].name: v for l, v in self.active_cfg.items()}, gain - over, over,
+                                            {self.lists[l].name: pick[l][1] for l in pick})
 
     def set_list_shares(self, mode):
         """After autotune(): 'whole' = every Winograd list layer on whole-unit shares (min_rounds -1), 'cut' = on stream-K shares
         (the best positive candidate is not re-timed: 4 rounds), anything else leaves the autotune's choice. For A/B runs of
         the two-frames-in-flight rate, which autotune()'s per-launch timing cannot see."""
         for l, (shape, mr) in list(self.active_cfg.items()):
-            if l in self.ACTIVE_SK or l in (self.ACTIVE_PAIR, self.ACTIVE_CONV):   # (the conv_0 / conv_1 lists are long: their share rule is the autotune's)
+            if self.lists[l].kind != "wino":   # (the conv_0 / conv_1 lists are long: their share rule is the autotune's)
                 continue
             if mode == "whole":
                 self.active_cfg[l] = (shape, -1)
@@ -1030,8 +1058,8 @@ class InferenceEngine:
         if not act:
             return {}
         n = self.ta.n_list.cpu().numpy()
-        M = self.ACTIVE_MASK
-        return {self.ACTIVE_SLOTS[l][0]: float(n[M[l]]) / (self.B * (self.ta.dims[M[l]][0] // 2) * (self.ta.dims[M[l]][1] // 2)) for l in act}
+        rows = [self.lists[l] for l in act]
+        return {r.name: float(n[r.mask]) / (self.B * (self.ta.dims[r.mask][0] // 2) * (self.ta.dims[r.mask][1] // 2)) for r in rows}
 
     # ------------------------------------------------------------------ the frame
     def enqueue(self, part=None):
@@ -1040,6 +1068,10 @@ class InferenceEngine:
         run (capture(split=True) keeps them as two graphs: EXPERIMENT bench.py --dense-token); None: the whole frame."""
         s = torch.cuda.current_stream().cuda_stream
         B = self.B
+        for l in self._active_layers():   # a configuration set by hand: refused before anything is launched
+            err = self._list_cfg_error(l, self.active_cfg[l])
+            if err is not None:
+                raise ValueError(err)
         if part == "back":
             return self._enqueue_body(s, "back")
         if self.cu_budget and (self.fork_front or self.fork_active):
@@ -1150,134 +1182,67 @@ class InferenceEngine:
         t, h, d = self.t, self.h, self.dn
         act = self._active_layers()
         if act and not forked_active and part != "back":
-            L4 = self.levels[-1]
-            if self._kmarks is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            self.ta.run(L4["indices"], L4["n"], L4["cap"])
-            fj = self._fill_jobs(act)
-            self.ta.fill(fj[0], fj[1], layers=fj[2], tiles=fj[3], near=fj[4], near_kind=fj[5])
-            if self._kmarks is not None:
-                e1.record()
-                self._kmarks.append(("tile_activity+fill", e0, e1))
+            def lists_and_fill():
+                L4 = self.levels[-1]
+                self.ta.run(L4["indices"], L4["n"], L4["cap"])
+                fj = self._fill_jobs(act)
+                self.ta.fill(fj[0], fj[1], layers=fj[2], tiles=fj[3], near=fj[4], near_kind=fj[5])
+            self._bracket("tile_activity+fill", lists_and_fill)
         if part == "front":
             return self.out
         if self.form == "rpn":
             return self._enqueue_predict(s, self._enqueue_rpn_neck())
-        x = self._conv(self.bev, d.b0[0], t["a"], name="b0.0", active=0 if 0 in act else None)
-        x = self._conv(x, d.b0[1], t["b"], name="b0.1", active=1 if 1 in act else None)
-        x0 = self._conv(x, d.b0[2], t["x0"], name="b0.2", active=2 if 2 in act else None)
-        y = self._conv(x0, d.b1[0], h["a"], name="b1.0", active=3 if 3 in act else None)
-        y = self._conv(y, d.b1[1], h["b"], name="b1.1", active=4 if 4 in act else None)
-        x1 = self._conv(y, d.b1[2], h["x1"], name="b1.2", active=5 if 5 in act else None)
-        tr0 = self._conv(x0, d.trans_0, t["tr0"], name="trans_0", active=6 if 6 in act else None)
-        tr1 = self._conv(x1, d.trans_1, h["tr1"], name="trans_1", active=7 if 7 in act else None)
-        cd = self.tile_cfg.get("deconv_0")
-        if self.ACTIVE_PAIR in act:
-            # both transposed convs over the 2x2 tiles of trans_1's map that can differ from the constant (or carry a residual that does)
-            (pa, sa, ta), (pb, sb, tb) = d.deconv_0, d.deconv_1
-            mp = self.ACTIVE_MASK[self.ACTIVE_PAIR]
-            if self._kmarks is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            if self.active_cfg[self.ACTIVE_PAIR][0] == PAIR_SPLIT_CFG:
-                ops.deconv2d_s2_pair_split_active(tr1, pa, pb, sa, ta, sb, tb, True, t["mid0"], t["mid1"], self.ta.tile_list[mp],
-                                                  self.ta.n_list[mp:mp + 1], residual_a=tr0)
-            else:
-                ops.deconv2d_s2_pair_active(tr1, pa, pb, sa, ta, sb, tb, True, t["mid0"], t["mid1"], self.ta.tile_list[mp],
-                                            self.ta.n_list[mp:mp + 1], residual_a=tr0, tile_cfg=self.active_cfg[self.ACTIVE_PAIR][0])
-            if self._kmarks is not None:
-                e1.record()
-                self._kmarks.append(("deconv_0+deconv_1", e0, e1))
-            mid0, mid1 = t["mid0"], t["mid1"]
-        elif self.merge_branch_convs and cd in (3, 4, 11, 12) and self.tile_cfg.get("deconv_1") in (3, 4, 11, 12) and self._tuning is None:
-            # both transposed convs read tr1: one launch over their 2 x 4 parity classes (same bits as two launches)
-            (pa, sa, ta), (pb, sb, tb) = d.deconv_0, d.deconv_1
-            if self._kmarks is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            ops.deconv2d_s2_pair(tr1, pa, pb, sa, ta, sb, tb, True, t["mid0"], t["mid1"], residual_a=tr0, tile_cfg=cd)
-            if self._kmarks is not None:
-                e1.record()
-                self._kmarks.append(("deconv_0+deconv_1", e0, e1))
-            mid0, mid1 = t["mid0"], t["mid1"]
-        else:
-            mid0 = self._conv(tr1, d.deconv_0, t["mid0"], residual=tr0, name="deconv_0")
-            mid1 = self._conv(tr1, d.deconv_1, t["mid1"], name="deconv_1")
-        c01 = self.tile_cfg.get("conv_0")
-        if self.ACTIVE_CONV in act:
-            # conv_0 / conv_1 over the tiles that can differ from the parity-class constants: one list, one launch per branch
-            shape, mr = self.active_cfg[self.ACTIVE_CONV]
-            mc = self.ACTIVE_MASK[self.ACTIVE_CONV]
-            if self._kmarks is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            for (pc, sc, sh), xin, xout in ((d.conv_0, mid0, t["o0"]), (d.conv_1, mid1, t["o1"])):
-                ops.conv2d_winograd_sk_active(xin, pc.upk_sk(shape), pc.cout, sc, sh, True, xout, shape, self.sk_ws, self.ta.tile_list[mc],
-                                              self.ta.n_list[mc:mc + 1], workgroups=self._wgs(shape), min_rounds=mr)
-            if self._kmarks is not None:
-                e1.record()
-                self._kmarks.append(("conv_0+conv_1", e0, e1))
-            o0, o1 = t["o0"], t["o1"]
-        elif self.merge_branch_convs and c01 in (22, 23, 24, 25) and self.tile_cfg.get("conv_1") == c01 and self._tuning is None \
-                and self.sk_ws is not None and self._branch_sets(c01 - 22) is not None:
-            sets = self._branch_sets(c01 - 22)
-            if self._kmarks is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            ops.conv2d_winograd_sk_sets(t["mid"], sets["upk"], 2, 128, sets["scale"], sets["shift"], True, t["o"], c01 - 22,
-                                        self.sk_ws, self._wgs(c01 - 22))
-            if self._kmarks is not None:
-                e1.record()
-                self._kmarks.append(("conv_0+conv_1", e0, e1))
-            o0, o1 = t["o0"], t["o1"]
-        else:
-            o0 = self._conv(mid0, d.conv_0, t["o0"], name="conv_0")
-            o1 = self._conv(mid1, d.conv_1, t["o1"], name="conv_1")
+        x = self._conv(self.bev, d.b0[0], t["a"], name="b0.0")
+        x = self._conv(x, d.b0[1], t["b"], name="b0.1")
+        x0 = self._conv(x, d.b0[2], t["x0"], name="b0.2")
+        y = self._conv(x0, d.b1[0], h["a"], name="b1.0")
+        y = self._conv(y, d.b1[1], h["b"], name="b1.1")
+        x1 = self._conv(y, d.b1[2], h["x1"], name="b1.2")
+        tr0 = self._conv(x0, d.trans_0, t["tr0"], name="trans_0")
+        tr1 = self._conv(x1, d.trans_1, h["tr1"], name="trans_1")
+        # the two transposed convs, then conv_0 / conv_1: over their tile list, else as one merged full-map launch, else one by one
+        def two_layers(kind, full_map):
+            l = self._kind_id[kind]
+            call = self._list_call(l, self.active_cfg[l]) if l in act else full_map()
+            if call is not None:
+                self._bracket(self.lists[l].name, call)
+            return call is not None
+        mid0, mid1, o0, o1 = t["mid0"], t["mid1"], t["o0"], t["o1"]
+        if not two_layers("pair", self._full_map_pair):
+            self._conv(tr1, d.deconv_0, mid0, residual=tr0, name="deconv_0")
+            self._conv(tr1, d.deconv_1, mid1, name="deconv_1")
+        if not two_layers("branches", self._full_map_branches):
+            self._conv(mid0, d.conv_0, o0, name="conv_0")
+            self._conv(mid1, d.conv_1, o1, name="conv_1")
         # ---- SSFA tail + heads (a10): one launch; the two-launch form stays for channel counts the fused kernel does not take
-        fused_keys = False
-        if self.fuse_head and d.head_w.shape[1] in (64, 128) and self._tuning is None:
-            if self._kmarks is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            fused_keys = True
-            ops.ssfa_fuse_head(o0, o1, d.w0, d.w1, *d.wbn, d.head_w, d.head_b, head_out=self.head,
-                               out=t["out"] if self.keep_ssfa else None, score_thresh=self.score_thresh,
-                               keys=self.keys if self.fuse_predict else None, key_count=self.key_count if self.fuse_predict else None,
-                               num_tasks=self.num_tasks)
-            if self._kmarks is not None:
-                e1.record()
-                self._kmarks.append(("ssfa_tail+head", e0, e1))
+        fused_keys = self.fuse_head and d.head_w.shape[1] in (64, 128) and self._tuning is None
+        if fused_keys:
+            self._bracket("ssfa_tail+head", lambda: ops.ssfa_fuse_head(
+                o0, o1, d.w0, d.w1, *d.wbn, d.head_w, d.head_b, head_out=self.head, out=t["out"] if self.keep_ssfa else None,
+                score_thresh=self.score_thresh, keys=self.keys if self.fuse_predict else None,
+                key_count=self.key_count if self.fuse_predict else None, num_tasks=self.num_tasks))
         else:
             ops.ssfa_fuse(o0, o1, d.w0, d.w1, *d.wbn, out=t["out"])
-            self._conv(t["out"], d.head, self.head.view(B, self.num_tasks * 22, self.H, self.W), relu=False, name="head")
+            self._conv(t["out"], d.head, self.head.view(self.B, self.num_tasks * 22, self.H, self.W), relu=False, name="head")
         self._mark("ssfa_head")
         return self._enqueue_predict(s, fused_keys)
 
     def _enqueue_rpn_neck(self):
         """The RPN neck (rpn_v1.py:107-116) + heads: the block's 3x3 layers, then the up-sampler + the heads of every task (+ the
         score-filter keys) in one launch, or as two ops.conv2d launches. Returns whether the launch wrote the keys."""
-        d, t, B = self.dn, self.t, self.B
-        act = self._active_layers()
+        d, t = self.dn, self.t
         x = self.bev
         for i, layer in enumerate(d.layers):
-            x = self._conv(x, layer, self._rpn_bufs[i + 1], name="blk0.%d" % i, active=i if i in act else None)
-        fused_keys = False
-        if self.fuse_head and self._tuning is None:
-            if self._kmarks is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            fused_keys = True
-            ops.rpn_up_head(x, d.up_w, d.up[1], d.up[2], d.head_w, d.head_b, head_out=self.head,
-                            out=t["out"] if self.keep_ssfa else None, score_thresh=self.score_thresh,
-                            keys=self.keys if self.fuse_predict else None, key_count=self.key_count if self.fuse_predict else None,
-                            num_tasks=self.num_tasks)
-            if self._kmarks is not None:
-                e1.record()
-                self._kmarks.append(("rpn_tail+head", e0, e1))
+            x = self._conv(x, layer, self._rpn_bufs[i + 1], name="blk0.%d" % i)
+        fused_keys = self.fuse_head and self._tuning is None
+        if fused_keys:
+            self._bracket("rpn_tail+head", lambda: ops.rpn_up_head(
+                x, d.up_w, d.up[1], d.up[2], d.head_w, d.head_b, head_out=self.head, out=t["out"] if self.keep_ssfa else None,
+                score_thresh=self.score_thresh, keys=self.keys if self.fuse_predict else None,
+                key_count=self.key_count if self.fuse_predict else None, num_tasks=self.num_tasks))
         else:
             self._conv(x, d.up, t["out"], name="up")
-            self._conv(t["out"], d.head, self.head.view(B, self.num_tasks * 22, self.H, self.W), relu=False, name="head")
+            self._conv(t["out"], d.head, self.head.view(self.B, self.num_tasks * 22, self.H, self.W), relu=False, name="head")
         self._mark("ssfa_head")
         return fused_keys
 
@@ -1420,15 +1385,7 @@ class InferenceEngine:
                 in_feat, dense = feat_last, True
             else:
                 dense = False
-            for _ in range(2):
-                self._sconv(lay, in_feat, nbr, tm, out_li, out_feat, st, dense=dense, idx=idx)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(reps):
-                self._sconv(lay, in_feat, nbr, tm, out_li, out_feat, st, dense=dense, idx=idx)
-            e1.record()
-            torch.cuda.synchronize()
-            ms = e0.elapsed_time(e1) / reps
+            ms = self._time(lambda: self._sconv(lay, in_feat, nbr, tm, out_li, out_feat, st, dense=dense, idx=idx), reps)
             use, exe = 2.0 * pairs * lay["cin"] * lay["cout"] / 1e9, 2.0 * steps * 16 * lay["cin"] * lay["cout"] / 1e9
             rows.append(dict(layer=idx, kind=lay["kind"], cin=lay["cin"], cout=lay["cout"], sites=n, pairs=pairs, tile_steps=steps,
                              sorted_tiles=srt,

@@ -227,3 +227,55 @@ def test_force_active_tiles_refuses_the_split_configuration_where_it_has_no_plan
         cfg[l] = (S2_SPLIT_CFG, 0)
         with pytest.raises(ValueError):
             eng.force_active_tiles(cfg)
+
+
+def test_list_candidates_and_hand_set_configurations(dev):
+    """What autotune() tries per list layer, in its order (default environment: all three SESSD_* switches on), and a configuration
+    a layer cannot run -- from force_active_tiles, or written into active_cfg by hand -- refused by name: by _list_cfg_error, by
+    _list_call, and by enqueue() before it launches anything (the frame's first launch clears the BEV map)."""
+    from sessd_hip import configs, synth
+    from sessd_hip.engine import InferenceEngine, PAIR_SPLIT_CFG, S2_SPLIT_CFG
+    VG = configs.VOXEL_GENERATOR
+    model = configs.build_synthetic_detector(dev, seed=0)
+    eng = InferenceEngine(model, VG["range"], VG["voxel_size"], 5, 16000, configs.TEST_CFG, 1, 20480, dev)
+    wino = [(shape, mr) for shape in (0, 1, 3) for mr in (1, 4, 8, 16, -1, -2)]
+    direct, sk = [(3, 0), (4, 0), (11, 0), (12, 0)], [(30, 1), (30, 4), (30, 8), (30, 16)]
+    want = {l: wino for l in (0, 1, 2, 4, 5)}
+    want[3] = sk + ([(S2_SPLIT_CFG, 0)] if eng.lists[3].layer[0].wsplit_s2() is not None else [])
+    want[6] = want[7] = direct + sk
+    want[8] = direct + ([(PAIR_SPLIT_CFG, 0)] if all(pc.wsplit() is not None for pc, _, _ in eng.lists[8].layer) else [])
+    want[9] = [(shape, mr) for shape in (0, 1, 3) for mr in (4, 8, 16, -1)]
+    assert sorted(eng.lists) == list(range(10))
+    for l in eng.lists:
+        assert list(eng._list_candidates(l)) == want[l], l
+        for cfg in want[l]:
+            assert eng._list_cfg_error(l, cfg) is None, (l, cfg)
+    assert want[3][-1] == (S2_SPLIT_CFG, 0) and want[8][-1] == (PAIR_SPLIT_CFG, 0)   # the benchmark model has both sets of planes
+    for l in (6, 0, eng.ACTIVE_PAIR):
+        assert "no split weight planes of a 3x3 stride-2 conv" in eng._list_cfg_error(l, (S2_SPLIT_CFG, 0))
+        with pytest.raises(ValueError):
+            eng._list_call(l, (S2_SPLIT_CFG, 0))
+    # a Winograd shape whose packing is missing: a number that is no shape, and b0.1 with a 24-channel weight (cin % 16: no 8-wave
+    # packing, the 4-wave one exists)
+    assert "no stream-K Winograd packing for shape 7" in eng._list_cfg_error(1, (7, 1))
+    _, scale, shift = eng.lists[1].layer
+    narrow = ops.pack_conv2d(torch.randn(128, 24, 3, 3).to(dev), 1)
+    assert narrow.upk_sk(0) is None and narrow.upk_sk(1) is not None
+    # the hand-set configurations: nothing of the frame is launched
+    eng.set_points([torch.from_numpy(synth.make_frame(51, 20000)).to(dev)])
+    eng.force_active_tiles()
+    row = eng.lists[1]
+    for l, cfg, repl in ((0, (S2_SPLIT_CFG, 0), None), (eng.ACTIVE_PAIR, (S2_SPLIT_CFG, 0), None), (1, (0, 1), (narrow, scale, shift))):
+        good = eng.active_cfg[l]
+        eng.active_cfg[l] = cfg
+        if repl is not None:
+            eng.lists[1] = row._replace(layer=repl)
+            assert "no stream-K Winograd packing for shape 0" in eng._list_cfg_error(1, (0, 1)) and eng._list_cfg_error(1, (1, 1)) is None
+        eng.bev.fill_(float("nan"))
+        with pytest.raises(ValueError):
+            eng.enqueue()
+        torch.cuda.synchronize()
+        assert torch.isnan(eng.bev).all(), l
+        eng.active_cfg[l], eng.lists[1] = good, row
+    eng.enqueue()
+    assert len(eng.results()) == 1 and not torch.isnan(eng.bev).any()

@@ -802,7 +802,7 @@ int sessd_ssfa_fuse_head(const float* x0, const float* x1, const float* w0, cons
 /* The same launch also running the score filter of MultiGroupHead.predict (mg_head_sessd.py:956-972: sigmoid(cls) >=
  * score_thresh, score *= ((iou + 1) / 2)^4) on the logits it has just produced: candidate keys (~score bits << 32 | anchor id,
  * anchor id = 2 * pixel + a) are appended to keys[b * key_cap ...], key_count[b] (device, zeroed by the caller) counts them.
- * Input of sessd_predict_fused (ext_keys / ext_key_count). keys == NULL: plain sessd_ssfa_fuse_head. */
+ * Input of sessd_predict (ext_keys / ext_key_count). keys == NULL: plain sessd_ssfa_fuse_head. */
 int sessd_ssfa_fuse_head_keys(const float* x0, const float* x1, const float* w0, const float* w1, float bn_scale0,
                               float bn_shift0, float bn_scale1, float bn_shift1, int batch, int channels, int num_pixels,
                               float* out, const float* head_w, const float* head_b, int nout, float* head_out,
@@ -813,7 +813,7 @@ int sessd_ssfa_fuse_head_keys(const float* x0, const float* x1, const float* w0,
  * (B, num_tasks, 22, num_pixels) planar = (B, num_tasks * 22, num_pixels); 1 <= num_tasks <= 4, one class and two rotations per
  * task. The maps are read and blended once per pixel, the heads run one after the other: task t's planes are bit for bit those
  * of sessd_ssfa_fuse_head_keys with task t's weights. keys (B * num_tasks, key_cap) / key_count (B * num_tasks, zeroed by the
- * caller): the score-filter keys per (frame, task), anchor id local to the task; input of sessd_predict_tasks. keys == NULL:
+ * caller): the score-filter keys per (frame, task), anchor id local to the task; input of sessd_predict. keys == NULL:
  * no score filter. num_tasks == 1 is sessd_ssfa_fuse_head_keys. */
 int sessd_ssfa_fuse_head_tasks(const float* x0, const float* x1, const float* w0, const float* w1, float bn_scale0,
                                float bn_shift0, float bn_scale1, float bn_shift1, int batch, int channels, int num_pixels,
@@ -837,67 +837,37 @@ int sessd_rpn_up_head_tasks(const float* x, const float* up_w, const float* up_s
  * replaces det3d/models/bbox_heads/mg_head_sessd.py:893-1057 (MultiGroupHead.predict / get_task_detections),
  * det3d/core/bbox/box_torch_ops.py:81-147 (second_box_decode) and :527-548 (rotate_nms), the CPU NMS of
  * det3d/ops/nms/nms_cpu.py:40-51 + nms_cpu.h:72-168 and the numba frustum test geometry.py:215-277.
- * head: (B,22,H*W) planar float32 -- ch 0..13 box codes (7 per anchor), 14..15 cls, 16..19 dir, 20..21 iou;
- * anchors (A,7) shared (anchors_per_frame = 0) or (B,A,7), A = 2*H*W; frustum (B,1,6,4,3) float64 or NULL.
- * Outputs (device): out_box (B,post,7), out_score (B,post), out_label (B,post) int32, out_count (B,). */
-size_t sessd_predict_workspace_bytes(int batch, int num_anchors, int pre_max_size, int post_max_size);
-int sessd_predict(const float* head, int batch, int num_pixels, const float* anchors, int anchors_per_frame,
-                  const double* frustum, float score_thresh, int pre_max_size, int post_max_size, float nms_iou_thresh,
-                  const float* post_center_range6, float direction_offset, float* out_box, float* out_score,
-                  int32_t* out_label, int32_t* out_count, void* workspace, size_t workspace_bytes,
-                  sessd_stream_t stream);
-/* sessd_predict with two optional fusions (same results): ext_keys / ext_key_count (both or neither) = the score-filter keys
- * (B, 2 * num_pixels) and per-frame counts already produced by sessd_ssfa_fuse_head_keys; records / record_counts / cursor
- * (all or none) = the frame's detection record written by the call's last launch (layout and ring rule of
- * sessd_pack_detections: slot = (*cursor + b) % capacity_frames, *cursor += batch). Three launches per call with both. */
-int sessd_predict_fused(const float* head, int batch, int num_pixels, const float* anchors, int anchors_per_frame,
-                        const double* frustum, float score_thresh, int pre_max_size, int post_max_size,
-                        float nms_iou_thresh, const float* post_center_range6, float direction_offset, float* out_box,
-                        float* out_score, int32_t* out_label, int32_t* out_count, const unsigned long long* ext_keys,
-                        const int32_t* ext_key_count, float* records, int32_t* record_counts, int capacity_frames,
-                        int32_t* cursor, void* workspace, size_t workspace_bytes, sessd_stream_t stream);
-/* Multi-task predict (mg_head_sessd.py:893-943: get_task_detections per task with its own anchors, concatenated in task order,
- * label = task index): head (B, num_tasks, 22, H*W) planar, 1 <= num_tasks <= 4, one class and two rotations per task; anchors
- * (num_tasks, A, 7) shared by all frames (anchors_per_frame = 0) or (B, num_tasks, A, 7) (anchors_per_frame = A), A = 2*H*W;
- * frustum (B,1,6,4,3) per frame or NULL. Every task applies score_thresh, pre_max_size, the NMS and post_max_size on its own.
- * Outputs: out_box (B, num_tasks*post, 7), out_score / out_label (B, num_tasks*post), out_count (B,): rows [0, out_count[b]) =
- * task 0's detections in NMS order, then task 1's, ...; out_task_count (B, num_tasks) or NULL = rows per task. ext_keys
- * (B*num_tasks, 2*H*W) / ext_key_count (B*num_tasks) from sessd_ssfa_fuse_head_tasks; records (capacity_frames,
- * num_tasks*post, 9) with the ring rule of sessd_pack_detections (*cursor += batch). num_tasks == 1 is sessd_predict_fused (same
- * launches, same workspace); num_tasks > 1 adds one small merge launch. */
-size_t sessd_predict_tasks_workspace_bytes(int batch, int num_tasks, int num_anchors, int pre_max_size, int post_max_size);
-int sessd_predict_tasks(const float* head, int batch, int num_tasks, int num_pixels, const float* anchors,
-                        int anchors_per_frame, const double* frustum, float score_thresh, int pre_max_size, int post_max_size,
-                        float nms_iou_thresh, const float* post_center_range6, float direction_offset, float* out_box,
-                        float* out_score, int32_t* out_label, int32_t* out_count, int32_t* out_task_count,
-                        const unsigned long long* ext_keys, const int32_t* ext_key_count, float* records,
-                        int32_t* record_counts, int capacity_frames, int32_t* cursor, void* workspace, size_t workspace_bytes,
-                        sessd_stream_t stream);
-/* sessd_predict_tasks with DI-NMS as the post-processor of every (frame, task): the other branch of get_task_detections
+ * One entry point, sessd_predict, whose arguments are the fields of sessd_predict_args_t (sessd_hip_types.h: shapes, settings,
+ * outputs and the optional inputs, each documented there). Per (frame, task): score filter (sigmoid(cls) >= score_thresh, score *=
+ * ((iou + 1) / 2)^4), top pre_max_size + box decode, NMS, at most post_max_size boxes, then frustum, direction fix and centre-range
+ * mask. Outputs (device): out_box (B, T*post, 7), out_score / out_label (B, T*post), out_count (B,): rows [0, out_count[b]) = task
+ * 0's detections in NMS order, then task 1's, ... (mg_head_sessd.py:893-943: get_task_detections per task with its own anchors,
+ * concatenated in task order, label = task index); out_task_count (B, T) or NULL = rows per task.
+ * Launches: with ext_keys and pre_max_size such that the suppression mask fits the LDS (<= ~1280) three per call -- top-k + decode,
+ * suppression mask, greedy walk + filters + record; without ext_keys a count clear and the score filter come first; num_tasks > 1
+ * runs the same launches over B * T virtual frames and adds one small merge launch.
+ * args->di != NULL: DI-NMS as the post-processor of every (frame, task), the other branch of get_task_detections
  * (mg_head_sessd.py:999-1018, box_torch_ops.rotate_weighted_nms with enable_centerness=True, centerness_c=False). Candidates as
- * in sessd_predict_tasks (score filter, IoU rectification, top pre_max_size); then per virtual frame, all on the device with the
+ * above (score filter, IoU rectification, top pre_max_size); then per virtual frame, all on the device with the
  * candidate count never leaving it: score_j *= (1 - softmax_j(|xy_j - anchor xy_j|))^centerness_pow (float32, max subtracted),
  * the core of nms_cpu.h:173-384 exactly as sessd_di_nms runs it with centerness_c = 0 (picks by the damped score, cnt summed in
  * box order, weighted-average boxes, suppress on overlap >= suppressed_thresh, keep when cnt > cnt_thresh), then frustum,
  * direction fix (the picked box's direction label) and centre-range mask on the AVERAGED boxes; score = the largest normalised
- * score of the pass * the normalisation maximum. Same arguments, outputs, record ring and multi-task merge as
- * sessd_predict_tasks; nms_iou_thresh is accepted and never read, like the reference's iou_threshold. pre_max_size <= 1024.
+ * score of the pass * the normalisation maximum. Same outputs, record ring and multi-task merge; nms_iou_thresh is accepted and
+ * never read, like the reference's iou_threshold. pre_max_size <= 1024.
  * Two deviations from the reference: (1) the anchors are the task's own (the reference reads task 0's x, y for every task --
  * the same grid in the KITTI configs); (2) CAPACITY: the reference wrapper ignores post_max_size, the outputs here hold
  * post_max_size rows per task, so the selection stops once post_max_size boxes are kept (= the reference's keep list cut at
- * post_max_size before the filters: later passes never change earlier kept boxes). di_truncated (B, num_tasks) int32 or NULL:
- * 1 where the loop stopped with unsuppressed candidates left, written 0 otherwise; di_truncated_sticky (one int32) or NULL: 1 is
- * ORed into it in that case, never cleared here. di_keep (B * num_tasks, post_max_size) / di_keep_count (B * num_tasks) int32,
- * both or neither: the kept candidates' ranks in the frame's top-k order and their number, BEFORE the filters (what the
- * reference returns as `selected`). 3 launches with external keys (+ the merge for num_tasks > 1). */
-size_t sessd_predict_di_workspace_bytes(int batch, int num_tasks, int num_anchors, int pre_max_size, int post_max_size);
-int sessd_predict_di(const float* head, int batch, int num_tasks, int num_pixels, const float* anchors, int anchors_per_frame,
-                     const double* frustum, float score_thresh, int pre_max_size, int post_max_size, float nms_iou_thresh,
-                     const float* post_center_range6, float direction_offset, float* out_box, float* out_score,
-                     int32_t* out_label, int32_t* out_count, int32_t* out_task_count, const unsigned long long* ext_keys,
-                     const int32_t* ext_key_count, float* records, int32_t* record_counts, int capacity_frames, int32_t* cursor,
-                     const sessd_di_cfg_t* di_cfg, int32_t* di_truncated, int32_t* di_truncated_sticky, int32_t* di_keep,
-                     int32_t* di_keep_count, void* workspace, size_t workspace_bytes, sessd_stream_t stream);
+ * post_max_size before the filters: later passes never change earlier kept boxes); di_truncated / di_truncated_sticky report
+ * where that happened, di_keep / di_keep_count the kept candidates' ranks BEFORE the filters (what the reference returns as
+ * `selected`). 3 launches with external keys (+ the merge for num_tasks > 1).
+ * Every argument is checked before any device call: SESSD_EINVAL for a NULL args and for what the kernels do not cover,
+ * SESSD_EWORKSPACE for a workspace below sessd_predict_workspace_bytes (num_anchors = 2 * num_pixels, di = 1 with DI-NMS), which
+ * returns 0 for batch < 1, num_tasks outside 1..4 and, with di, pre_max_size outside 1..1024. sessd_predict_args_bytes: sizeof
+ * the struct, for a binding's ABI check. */
+size_t sessd_predict_workspace_bytes(int batch, int num_tasks, int num_anchors, int pre_max_size, int post_max_size, int di);
+int sessd_predict(const sessd_predict_args_t* args, void* workspace, size_t workspace_bytes, sessd_stream_t stream);
+size_t sessd_predict_args_bytes(void);
 /* spconv.utils.rbbox_iou / rbbox_intersection (third-party spconv v1, imported by det3d/core/bbox/box_np_ops.py:9 for riou_cc /
  * rinter_cc :20-50): pairwise IoU (mode 0) or intersection area (mode 1) of convex quads given as corners (n,4,2) x (k,4,2);
  * pairs whose caller-supplied stand-up IoU is <= standup_thresh stay 0. standup_iou and out are (n,k) row-major. */

@@ -95,7 +95,7 @@ typedef struct {
   float center_range[6];                            /* post_center_range (mg_head_sessd.py:484) */
 } sessd_head_loss_cfg_t;
 
-/* DI-NMS settings of sessd_predict_di: the arguments get_task_detections passes to box_torch_ops.rotate_weighted_nms
+/* DI-NMS settings of sessd_predict (args->di): the arguments get_task_detections passes to box_torch_ops.rotate_weighted_nms
  * (mg_head_sessd.py:1012-1017: centerness_pow 2, nms_cnt_thresh 2.6, intervals (0, 20, 40, 60), sigma squares (0.0009, 0.009,
  * 0.1, 1), suppressed_thresh 0.3). interval[0 .. n_interval) are the distance bounds, sigma_sq[k] belongs to
  * [interval[k], interval[k + 1]): n_interval - 1 entries are read. */
@@ -104,5 +104,50 @@ typedef struct {
   int32_t n_interval;        /* <= 8 */
   float interval[8], sigma_sq[8];
 } sessd_di_cfg_t;
+
+/* The arguments of sessd_predict (sessd_hip.h documents the launches and the DI-NMS semantics). B = batch, T = num_tasks,
+ * A = 2 * num_pixels anchors per task, post = post_max_size. Every pointer is a device pointer except `di`; an optional one is
+ * NULL when absent. */
+typedef struct {
+  /* inputs */
+  const float* head;           /* (B, T, 22, num_pixels) planar float32: per task ch 0..13 box codes (7 per anchor), 14..15 cls,
+                                  16..19 dir, 20..21 iou (one class and two rotations per task) */
+  int32_t batch;
+  int32_t num_tasks;           /* 1..4; (frame, task) runs as the virtual frame b * T + t */
+  int32_t num_pixels;          /* H * W */
+  const float* anchors;        /* (T, A, 7) shared by all frames, or (B, T, A, 7) */
+  int32_t anchors_per_frame;   /* 0: shared anchors; A: per-frame anchors */
+  const double* frustum;      /* (B, 1, 6, 4, 3) float64 per real frame, or NULL */
+  /* settings: every task applies score_thresh, pre_max_size, the NMS and post_max_size on its own */
+  float score_thresh;
+  int32_t pre_max_size;        /* <= 1984; <= 1024 with di */
+  int32_t post_max_size;
+  float nms_iou_thresh;        /* with di: accepted and never read, like the reference's iou_threshold */
+  float post_center_range[6];  /* by value */
+  float direction_offset;
+  /* outputs: rows [0, out_count[b]) are frame b's detections -- task 0's in NMS order, then task 1's, ...; label = task index */
+  float* out_box;              /* (B, T * post, 7) */
+  float* out_score;            /* (B, T * post) */
+  int32_t* out_label;          /* (B, T * post) */
+  int32_t* out_count;          /* (B,) */
+  int32_t* out_task_count;     /* (B, T) or NULL: the rows each task contributed */
+  /* optional, both or neither: the score-filter keys (B * T, A) uint64 and their per-(frame, task) counts already produced with
+   * the head tensor (sessd_ssfa_fuse_head_tasks / sessd_rpn_up_head_tasks; anchor id local to the task) -- the count clear and
+   * the score-filter launch are skipped */
+  const uint64_t* ext_keys;
+  const int32_t* ext_key_count;
+  /* optional, all or none: every frame also leaves its fixed-size detection record (T * post, 9) from inside the call's last
+   * launch, with the layout and ring rule of sessd_pack_detections: slot = (*cursor + b) % capacity_frames, *cursor += batch */
+  float* records;              /* (capacity_frames, T * post, 9) */
+  int32_t* record_counts;      /* (capacity_frames,) */
+  int32_t capacity_frames;     /* >= batch; batch <= 256 */
+  int32_t* cursor;             /* one device int */
+  /* optional: DI-NMS instead of the greedy rotated NMS (NULL) */
+  const sessd_di_cfg_t* di;    /* HOST pointer, read before the call returns */
+  int32_t* di_truncated;       /* (B, T) or NULL: 1 where the selection stopped with unsuppressed candidates left, else 0 */
+  int32_t* di_truncated_sticky;/* one int32 or NULL: 1 is ORed into it in that case, never cleared by the call */
+  int32_t* di_keep;            /* (B * T, post) / di_keep_count (B * T), both or neither: the kept candidates' ranks in the */
+  int32_t* di_keep_count;      /* frame's top-k order and their number, BEFORE the filters (the reference's `selected`) */
+} sessd_predict_args_t;
 
 #endif

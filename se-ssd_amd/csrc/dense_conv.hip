@@ -1239,7 +1239,7 @@ int sessd_ssfa_fuse(const float* x0, const float* x1, const float* w0, const flo
 // keys != NULL: the launch also runs the score filter of predict (score_thresh on sigmoid(cls), IoU-rectified score) and
 // appends the candidates' 64-bit keys (~score bits << 32 | anchor id, anchor id = 2 * pixel + a, local to the task) to
 // keys[(b * num_tasks + t) * key_cap ..] with key_count[b * num_tasks + t] (zeroed by the caller) counting them -- what
-// sessd_predict_tasks takes as ext_keys / ext_key_count.
+// sessd_predict takes as ext_keys / ext_key_count.
 int sessd_ssfa_fuse_head_tasks(const float* x0, const float* x1, const float* w0, const float* w1, float bn_scale0, float bn_shift0,
                                float bn_scale1, float bn_shift1, int batch, int channels, int num_pixels, float* out,
                                const float* head_w, const float* head_b, int num_tasks, float* head_out, float score_thresh,

@@ -998,36 +998,49 @@ __global__ __launch_bounds__(64) void nms_reduce_batch_kernel(const int* __restr
 
 extern "C" {
 
-size_t sessd_predict_tasks_workspace_bytes(int batch, int num_tasks, int num_anchors, int pre_max_size, int post_max_size) {
+// 0 for batch < 1, num_tasks outside 1..4 and, with di, pre_max_size outside 1..1024
+size_t sessd_predict_workspace_bytes(int batch, int num_tasks, int num_anchors, int pre_max_size, int post_max_size, int di) {
   if (batch < 1 || num_tasks < 1 || num_tasks > 4) return 0;
-  return post_ws_layout(batch * num_tasks, num_tasks, num_anchors, pre_max_size, post_max_size, nullptr, nullptr);
+  if (di && (pre_max_size < 1 || pre_max_size > DI_MAXN)) return 0;
+  return post_ws_layout(batch * num_tasks, num_tasks, num_anchors, pre_max_size, post_max_size, nullptr, nullptr, di != 0);
 }
 
-size_t sessd_predict_workspace_bytes(int batch, int num_anchors, int pre_max_size, int post_max_size) {
-  return post_ws_layout(batch, 1, num_anchors, pre_max_size, post_max_size, nullptr, nullptr);
-}
+size_t sessd_predict_args_bytes(void) { return sizeof(sessd_predict_args_t); }
 
-// head (B,T,22,H*W) planar, T = num_tasks (1..4, one class and two rotations per task); anchors (T,A,7) shared by all frames
-// (anchors_per_frame = 0) or (B,T,A,7) (anchors_per_frame = A), A = 2 * num_pixels per task; frustum (B,1,6,4,3) float64 or
-// NULL, per real frame. Every task applies the score threshold, pre_max_size, the NMS and post_max_size on its own.
-// Outputs: out_box (B,T*post,7), out_score (B,T*post), out_label (B,T*post) int32, out_count (B,) -- rows [0,out_count[b]) are
-// the detections of frame b: task 0's in NMS order, then task 1's, ...; label = task index. out_task_count (B,T) or NULL: the
-// rows each task contributed.
-// ext_keys / ext_key_count (both or neither): the score-filter keys (B*T, 2 * num_pixels) uint64 and their per-(frame, task)
-// counts were already produced with the head tensor (sessd_ssfa_fuse_head_tasks; counts zeroed by the caller before that
-// launch) -- the count clear and the score_filter launch are skipped.
-// records != NULL: every frame also leaves its fixed-size detection record (T*post, 9) (sessd_pack_detections' layout and ring
-// rule: slot = (*cursor + b) % capacity_frames, *cursor += batch) from inside the last launch.
+// The post-processor of a batch; the arguments are documented field by field at sessd_predict_args_t (sessd_hip_types.h).
 // T = 1: 3 launches per call with external keys and pre_max_size such that the suppression mask fits the LDS (<= ~1280): top-k
 // + decode, suppression mask, greedy walk + filters + record. T > 1: the same launches over B*T virtual frames + the merge.
-// di != nullptr: DI-NMS (sessd_predict_di) instead of the suppression mask and the greedy walk; everything else is shared
-static int predict_impl(const float* head, int batch, int num_tasks, int num_pixels, const float* anchors, int anchors_per_frame,
-                        const double* frustum, float score_thresh, int pre_max_size, int post_max_size, float nms_iou_thresh,
-                        const float* post_center_range6, float direction_offset, float* out_box, float* out_score,
-                        int* out_label, int* out_count, int* out_task_count, const unsigned long long* ext_keys,
-                        const int* ext_key_count, float* records, int* record_counts, int capacity_frames, int* cursor,
-                        const DiCfg* di, int* di_truncated, int* di_truncated_sticky, int* di_keep, int* di_keep_count,
-                        void* workspace, size_t workspace_bytes, hipStream_t stream) {
+// di != nullptr: DI-NMS (box_torch_ops.rotate_weighted_nms, enable_centerness=True, centerness_c=False) instead of the suppression
+// mask and the greedy walk, everything else is shared: see the kernels above and include/sessd_hip.h. 3 launches per call with
+// external keys (top-k + decode, overlap rows, selection + filters + record), one fewer than the greedy path; T > 1 adds the merge.
+int sessd_predict(const sessd_predict_args_t* args, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (!args) return SESSD_EINVAL;
+  const sessd_predict_args_t& a = *args;
+  const float *head = a.head, *anchors = a.anchors, *post_center_range6 = a.post_center_range;
+  const double* frustum = a.frustum;
+  const int batch = a.batch, num_tasks = a.num_tasks, num_pixels = a.num_pixels, anchors_per_frame = a.anchors_per_frame;
+  const int pre_max_size = a.pre_max_size, post_max_size = a.post_max_size, capacity_frames = a.capacity_frames;
+  const float score_thresh = a.score_thresh, nms_iou_thresh = a.nms_iou_thresh, direction_offset = a.direction_offset;
+  float *out_box = a.out_box, *out_score = a.out_score, *records = a.records;
+  int *out_label = a.out_label, *out_count = a.out_count, *out_task_count = a.out_task_count;
+  int *record_counts = a.record_counts, *cursor = a.cursor;
+  const unsigned long long* ext_keys = (const unsigned long long*)a.ext_keys;
+  const int* ext_key_count = a.ext_key_count;
+  int *di_truncated = a.di_truncated, *di_truncated_sticky = a.di_truncated_sticky, *di_keep = a.di_keep;
+  int* di_keep_count = a.di_keep_count;
+  if (a.di && (a.di->n_interval < 0 || a.di->n_interval > 8)) return SESSD_EINVAL;
+  DiCfg D;
+  const DiCfg* di = a.di ? &D : nullptr;
+  if (a.di) {
+    D.cnt_thresh = a.di->cnt_thresh;
+    D.suppressed_thresh = a.di->suppressed_thresh;
+    D.centerness_pow = a.di->centerness_pow;
+    D.n_interval = a.di->n_interval;
+    for (int k = 0; k < 8; ++k) {
+      D.interval[k] = k < D.n_interval ? a.di->interval[k] : 0.f;
+      D.sigma_sq[k] = k + 1 < D.n_interval ? a.di->sigma_sq[k] : 1.f;
+    }
+  }
   if (batch < 1 || num_pixels < 1 || pre_max_size < 1 || pre_max_size > 4096 || post_max_size < 1) return SESSD_EINVAL;
   if (di && pre_max_size > DI_MAXN) return SESSD_EINVAL;  // one thread per candidate in the selection workgroup
   if ((di_keep == nullptr) != (di_keep_count == nullptr)) return SESSD_EINVAL;
@@ -1123,71 +1136,6 @@ static int predict_impl(const float* head, int batch, int num_tasks, int num_pix
     SESSD_CHECK_LAUNCH();
   }
   return SESSD_OK;
-}
-
-int sessd_predict_tasks(const float* head, int batch, int num_tasks, int num_pixels, const float* anchors, int anchors_per_frame,
-                        const double* frustum, float score_thresh, int pre_max_size, int post_max_size, float nms_iou_thresh,
-                        const float* post_center_range6, float direction_offset, float* out_box, float* out_score,
-                        int* out_label, int* out_count, int* out_task_count, const unsigned long long* ext_keys,
-                        const int* ext_key_count, float* records, int* record_counts, int capacity_frames, int* cursor,
-                        void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  return predict_impl(head, batch, num_tasks, num_pixels, anchors, anchors_per_frame, frustum, score_thresh, pre_max_size,
-                      post_max_size, nms_iou_thresh, post_center_range6, direction_offset, out_box, out_score, out_label, out_count,
-                      out_task_count, ext_keys, ext_key_count, records, record_counts, capacity_frames, cursor, nullptr, nullptr,
-                      nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
-}
-
-size_t sessd_predict_di_workspace_bytes(int batch, int num_tasks, int num_anchors, int pre_max_size, int post_max_size) {
-  if (batch < 1 || num_tasks < 1 || num_tasks > 4 || pre_max_size < 1 || pre_max_size > DI_MAXN) return 0;
-  return post_ws_layout(batch * num_tasks, num_tasks, num_anchors, pre_max_size, post_max_size, nullptr, nullptr, true);
-}
-
-// sessd_predict_tasks with DI-NMS (box_torch_ops.rotate_weighted_nms, enable_centerness=True, centerness_c=False) as the
-// post-processor of every (frame, task): see the kernels above and include/sessd_hip.h. nms_iou_thresh is accepted and never read,
-// as in the reference. 3 launches per call with external keys (top-k + decode, overlap rows, selection + filters + record), one
-// fewer than the greedy path; T > 1 adds the merge.
-int sessd_predict_di(const float* head, int batch, int num_tasks, int num_pixels, const float* anchors, int anchors_per_frame,
-                     const double* frustum, float score_thresh, int pre_max_size, int post_max_size, float nms_iou_thresh,
-                     const float* post_center_range6, float direction_offset, float* out_box, float* out_score, int* out_label,
-                     int* out_count, int* out_task_count, const unsigned long long* ext_keys, const int* ext_key_count,
-                     float* records, int* record_counts, int capacity_frames, int* cursor, const sessd_di_cfg_t* di_cfg,
-                     int* di_truncated, int* di_truncated_sticky, int* di_keep, int* di_keep_count, void* workspace,
-                     size_t workspace_bytes, hipStream_t stream) {
-  if (!di_cfg || di_cfg->n_interval < 0 || di_cfg->n_interval > 8) return SESSD_EINVAL;
-  DiCfg D;
-  D.cnt_thresh = di_cfg->cnt_thresh;
-  D.suppressed_thresh = di_cfg->suppressed_thresh;
-  D.centerness_pow = di_cfg->centerness_pow;
-  D.n_interval = di_cfg->n_interval;
-  for (int k = 0; k < 8; ++k) {
-    D.interval[k] = k < D.n_interval ? di_cfg->interval[k] : 0.f;
-    D.sigma_sq[k] = k + 1 < D.n_interval ? di_cfg->sigma_sq[k] : 1.f;
-  }
-  return predict_impl(head, batch, num_tasks, num_pixels, anchors, anchors_per_frame, frustum, score_thresh, pre_max_size,
-                      post_max_size, nms_iou_thresh, post_center_range6, direction_offset, out_box, out_score, out_label, out_count,
-                      out_task_count, ext_keys, ext_key_count, records, record_counts, capacity_frames, cursor, &D, di_truncated,
-                      di_truncated_sticky, di_keep, di_keep_count, workspace, workspace_bytes, stream);
-}
-
-int sessd_predict_fused(const float* head, int batch, int num_pixels, const float* anchors, int anchors_per_frame,
-                        const double* frustum, float score_thresh, int pre_max_size, int post_max_size, float nms_iou_thresh,
-                        const float* post_center_range6, float direction_offset, float* out_box, float* out_score,
-                        int* out_label, int* out_count, const unsigned long long* ext_keys, const int* ext_key_count,
-                        float* records, int* record_counts, int capacity_frames, int* cursor, void* workspace,
-                        size_t workspace_bytes, hipStream_t stream) {
-  return sessd_predict_tasks(head, batch, 1, num_pixels, anchors, anchors_per_frame, frustum, score_thresh, pre_max_size,
-                             post_max_size, nms_iou_thresh, post_center_range6, direction_offset, out_box, out_score, out_label,
-                             out_count, nullptr, ext_keys, ext_key_count, records, record_counts, capacity_frames, cursor,
-                             workspace, workspace_bytes, stream);
-}
-
-int sessd_predict(const float* head, int batch, int num_pixels, const float* anchors, int anchors_per_frame,
-                  const double* frustum, float score_thresh, int pre_max_size, int post_max_size, float nms_iou_thresh,
-                  const float* post_center_range6, float direction_offset, float* out_box, float* out_score,
-                  int* out_label, int* out_count, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  return sessd_predict_fused(head, batch, num_pixels, anchors, anchors_per_frame, frustum, score_thresh, pre_max_size,
-                             post_max_size, nms_iou_thresh, post_center_range6, direction_offset, out_box, out_score, out_label,
-                             out_count, nullptr, nullptr, nullptr, nullptr, 0, nullptr, workspace, workspace_bytes, stream);
 }
 
 // Stand-alone rotated NMS with the predict-path semantics (box_torch_ops.rotate_nms after its topk):

@@ -55,6 +55,16 @@ class DiCfg(C.Structure):
                 ("interval", f32 * 8), ("sigma_sq", f32 * 8)]
 
 
+class PredictArgs(C.Structure):
+    """sessd_predict_args_t (include/sessd_hip_types.h)"""
+    _fields_ = [("head", vp), ("batch", i32), ("num_tasks", i32), ("num_pixels", i32), ("anchors", vp), ("anchors_per_frame", i32),
+                ("frustum", vp), ("score_thresh", f32), ("pre_max_size", i32), ("post_max_size", i32), ("nms_iou_thresh", f32),
+                ("post_center_range", f32 * 6), ("direction_offset", f32), ("out_box", vp), ("out_score", vp), ("out_label", vp),
+                ("out_count", vp), ("out_task_count", vp), ("ext_keys", vp), ("ext_key_count", vp), ("records", vp),
+                ("record_counts", vp), ("capacity_frames", i32), ("cursor", vp), ("di", C.POINTER(DiCfg)), ("di_truncated", vp),
+                ("di_truncated_sticky", vp), ("di_keep", vp), ("di_keep_count", vp)]
+
+
 # name -> (restype, argtypes). Kept in step with include/sessd_hip.h (tests/test_abi.py checks it).
 SIGNATURES = {
     "sessd_version": (C.c_char_p, []),
@@ -135,18 +145,12 @@ SIGNATURES = {
     "sessd_deconv2d_s2_mfma": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp]),
     "sessd_ssfa_fuse": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, vp, vp]),
     "sessd_ssfa_fuse_head": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
-    "sessd_predict_workspace_bytes": (sz, [i32, i32, i32, i32]),
-    "sessd_predict": (i32, [vp, i32, i32, vp, i32, vp, f32, i32, i32, f32, vp, f32, vp, vp, vp, vp, vp, sz, vp]),
-    "sessd_predict_fused": (i32, [vp, i32, i32, vp, i32, vp, f32, i32, i32, f32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, sz, vp]),
+    "sessd_predict_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+    "sessd_predict": (i32, [C.POINTER(PredictArgs), vp, sz, vp]),
+    "sessd_predict_args_bytes": (sz, []),
     "sessd_ssfa_fuse_head_keys": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, i32, vp, vp]),
     "sessd_ssfa_fuse_head_tasks": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, i32, vp, vp]),
     "sessd_rpn_up_head_tasks": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, i32, vp, vp]),
-    "sessd_predict_tasks_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
-    "sessd_predict_tasks": (i32, [vp, i32, i32, i32, vp, i32, vp, f32, i32, i32, f32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp,
-                                  sz, vp]),
-    "sessd_predict_di_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
-    "sessd_predict_di": (i32, [vp, i32, i32, i32, vp, i32, vp, f32, i32, i32, f32, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp,
-                               vp, vp, vp, vp, vp, sz, vp]),
     "sessd_di_nms_workspace_bytes": (sz, [i32]),
     "sessd_di_nms": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, f32, vp, i32, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "sessd_pack_detections": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp]),

@@ -374,7 +374,45 @@ class RpnPlan:
         return {i: tuned[min(i, 5)] for i in range(len(self.layers))}
 
 
-class InferenceEngine:
+class FrameEngine:
+    """What the whole-frame engines share around their predict stage: the device ring of detection records and the synchronising
+    read-back. A subclass has B, dev, num_tasks, post_max (a frame's record holds num_tasks * post_max rows), out, graph, the
+    sticky device flag err and its message err_text."""
+    records = record_counts = record_cursor = None
+
+    def attach_records(self, capacity_frames):
+        """Keep every frame's detections on the device as a fixed-size record (capacity_frames, num_tasks * post_max, 9) [box 7 |
+        score | label] + counts, appended by the frame's own last launch (also inside a captured graph, hence before capture())."""
+        if self.graph is not None or getattr(self, "graph_front", None) is not None:
+            raise RuntimeError("attach_records must precede capture(): the ring's address is baked into the graph")
+        cap = max(int(capacity_frames), self.B)
+        self.records = torch.zeros((cap, self.num_tasks * self.post_max, 9), dtype=torch.float32, device=self.dev)
+        self.record_counts = torch.zeros((cap,), dtype=torch.int32, device=self.dev)
+        self.record_cursor = torch.zeros((1,), dtype=torch.int32, device=self.dev)
+        return self.records, self.record_counts
+
+    def _record_ring(self):
+        """launch()'s `records` of the frame: the attached ring, or None"""
+        return None if self.records is None else (self.records, self.record_counts, self.record_cursor)
+
+    def results(self):
+        """The one synchronising read-back: list of dict(box3d_lidar, scores, label_preds) numpy per frame; raises err_text (once,
+        then re-armed) when the sticky device flag is set."""
+        cnt = self.out["count"].cpu().numpy()
+        if int(self.err.item()) != 0:
+            self.err.zero_()
+            raise RuntimeError(self.err_text)
+        res = []
+        for b in range(self.B):
+            n = int(cnt[b])
+            res.append(dict(box3d_lidar=self.out["box"][b, :n].cpu().numpy(), scores=self.out["score"][b, :n].cpu().numpy(),
+                            label_preds=self.out["label"][b, :n].cpu().numpy().astype(np.int64)))
+        return res
+
+
+class InferenceEngine(FrameEngine):
+    err_text = "sparse level capacity overflow: raise `growth` or max_voxels"
+
     def __init__(self, model, voxel_range, voxel_size, max_points_per_voxel, max_voxels, test_cfg, batch_size=1,
                  max_points_per_frame=32768, device=None, growth=(1.5, 1.0, 0.75, 0.75), anchors=None,
                  use_frustum=False, allow_winograd=True, sort_sites=False, sort_tiles=False, active_tiles=True):
@@ -387,7 +425,6 @@ class InferenceEngine:
         # before anything touches the device
         nms = test_cfg["nms"] if isinstance(test_cfg, dict) else test_cfg.nms
         self.nms_type, self.di = ops.nms_settings(nms, int(nms["nms_pre_max_size"]))
-        self.di_cfg = ops.check_di(self.di) if self.di is not None else None
         # the neck's form: "ssfa" (DensePlan) or "rpn" (RpnPlan: the SECOND-style neck of the three-class config, whose limits are
         # checked here, too)
         self.form = "rpn" if type(model.neck).__name__ == "RPN" else "ssfa"
@@ -553,14 +590,19 @@ class InferenceEngine:
                         count=torch.zeros((B,), dtype=i32, device=dev))
         if T > 1:
             self.out["task_count"] = torch.zeros((B, T), dtype=i32, device=dev)
-        ws_bytes = lib.sessd_predict_tasks_workspace_bytes if self.di_cfg is None else lib.sessd_predict_di_workspace_bytes
-        self.pred_ws = torch.empty(int(ws_bytes(B, T, 2 * H * W, self.pre_max, self.post_max)), dtype=torch.uint8, device=dev)
+        self.pred_ws = torch.empty(int(lib.sessd_predict_workspace_bytes(B, T, 2 * H * W, self.pre_max, self.post_max,
+                                                                         0 if self.di is None else 1)), dtype=torch.uint8, device=dev)
         # DI-NMS keeps at most post_max boxes per (frame, task) (the reference's wrapper has no cap): di_truncated (B, T) says where
         # the selection stopped with candidates left, nms_truncated is the STICKY OR over all frames so far (outside every per-frame
         # clear, like self.err; nothing raises on it)
         self.nms_truncated = torch.zeros((1,), dtype=i32, device=dev)
-        if self.di_cfg is not None:
+        if self.di is not None:
             self.out["di_truncated"] = torch.zeros((B, T), dtype=i32, device=dev)
+        # (a11-a14) top-k + decode, suppression mask, greedy walk + filters (+ the frame's record): 3 launches with the head's keys;
+        # DI-NMS: overlap rows and selection + filters in place of mask and walk; T > 1: the same over B * T virtual frames + the merge
+        self.predict = ops.Predict(B, T, H * W, self.anchors, self.frustum, self.score_thresh, self.pre_max, self.post_max,
+                                   self.nms_thresh, self.post_range, self.dir_offset, self.nms_type, self.di, dev, out=self.out,
+                                   workspace=self.pred_ws, sticky=self.nms_truncated)
         self.keys = torch.empty((B * T, 2 * H * W), dtype=torch.int64, device=dev)  # score-filter keys written by the head launch
         self.fuse_predict = True  # score filter inside the head launch; NMS walk + filters + record in one launch
         self.batched_voxelizer = True  # the frames of a batch in four launches (False: four per frame, as round 3)
@@ -610,7 +652,6 @@ class InferenceEngine:
             self.renum_ws = torch.empty(int(lib.sessd_sparse_renumber_workspace_bytes(B, self._hash0_dims.data_ptr())),
                                         dtype=torch.uint8, device=dev)
         self._ks = {}
-        self.records = None
         self._npts = [0] * B
         self.graph = None
         self._marks = None
@@ -1247,57 +1288,10 @@ class InferenceEngine:
         return fused_keys
 
     def _enqueue_predict(self, s, fused_keys):
-        B = self.B
-        # ---- predict (a11-a14): top-k + decode, suppression mask, greedy walk + filters (+ the frame's record): 3 launches
         use_keys = fused_keys and self.fuse_predict
-        rec = self.records is not None
-        if self.di_cfg is not None:  # DI-NMS: top-k + decode, overlap rows, selection + filters (+ record) (+ the merge for T > 1)
-            import ctypes
-            check(lib.sessd_predict_di(self.head.data_ptr(), B, self.num_tasks, self.H * self.W, self.anchors.data_ptr(), 0,
-                                       0 if self.frustum is None else self.frustum.data_ptr(), self.score_thresh, self.pre_max,
-                                       self.post_max, self.nms_thresh, self.post_range.data_ptr(), self.dir_offset,
-                                       self.out["box"].data_ptr(), self.out["score"].data_ptr(), self.out["label"].data_ptr(),
-                                       self.out["count"].data_ptr(), self.out["task_count"].data_ptr() if self.num_tasks > 1 else 0,
-                                       self.keys.data_ptr() if use_keys else 0, self.key_count.data_ptr() if use_keys else 0,
-                                       self.records.data_ptr() if rec else 0, self.record_counts.data_ptr() if rec else 0,
-                                       self.records.shape[0] if rec else 0, self.record_cursor.data_ptr() if rec else 0,
-                                       ctypes.addressof(self.di_cfg), self.out["di_truncated"].data_ptr(),
-                                       self.nms_truncated.data_ptr(), 0, 0, self.pred_ws.data_ptr(), self.pred_ws.numel(), s),
-                  "predict_di")
-            self._mark("predict")
-            return self.out
-        if self.num_tasks > 1:  # the same launches over B * T virtual frames + the merge in task order
-            check(lib.sessd_predict_tasks(self.head.data_ptr(), B, self.num_tasks, self.H * self.W, self.anchors.data_ptr(), 0,
-                                          0 if self.frustum is None else self.frustum.data_ptr(), self.score_thresh, self.pre_max,
-                                          self.post_max, self.nms_thresh, self.post_range.data_ptr(), self.dir_offset,
-                                          self.out["box"].data_ptr(), self.out["score"].data_ptr(), self.out["label"].data_ptr(),
-                                          self.out["count"].data_ptr(), self.out["task_count"].data_ptr(),
-                                          self.keys.data_ptr() if use_keys else 0, self.key_count.data_ptr() if use_keys else 0,
-                                          self.records.data_ptr() if rec else 0, self.record_counts.data_ptr() if rec else 0,
-                                          self.records.shape[0] if rec else 0, self.record_cursor.data_ptr() if rec else 0,
-                                          self.pred_ws.data_ptr(), self.pred_ws.numel(), s), "predict_tasks")
-            self._mark("predict")
-            return self.out
-        check(lib.sessd_predict_fused(self.head.data_ptr(), B, self.H * self.W, self.anchors.data_ptr(), 0,
-                                      0 if self.frustum is None else self.frustum.data_ptr(), self.score_thresh, self.pre_max,
-                                      self.post_max, self.nms_thresh, self.post_range.data_ptr(), self.dir_offset,
-                                      self.out["box"].data_ptr(), self.out["score"].data_ptr(), self.out["label"].data_ptr(),
-                                      self.out["count"].data_ptr(), self.keys.data_ptr() if use_keys else 0,
-                                      self.key_count.data_ptr() if use_keys else 0,
-                                      self.records.data_ptr() if rec else 0, self.record_counts.data_ptr() if rec else 0,
-                                      self.records.shape[0] if rec else 0, self.record_cursor.data_ptr() if rec else 0,
-                                      self.pred_ws.data_ptr(), self.pred_ws.numel(), s), "predict_fused")
+        self.predict.launch(self.head, (self.keys, self.key_count) if use_keys else None, self._record_ring(), s)
         self._mark("predict")
         return self.out
-
-    def attach_records(self, capacity_frames):
-        """Keep every frame's detections on the device as a fixed-size record (capacity_frames, num_tasks * post_max, 9) [box 7 |
-        score | label] + counts, appended by the frame itself (also inside a captured graph; call before capture())."""
-        cap = max(int(capacity_frames), self.B)
-        self.records = torch.zeros((cap, self.num_tasks * self.post_max, 9), dtype=torch.float32, device=self.dev)
-        self.record_counts = torch.zeros((cap,), dtype=torch.int32, device=self.dev)
-        self.record_cursor = torch.zeros((1,), dtype=torch.int32, device=self.dev)
-        return self.records, self.record_counts
 
     def _mark(self, name):
         if self._marks is not None:
@@ -1433,16 +1427,3 @@ class InferenceEngine:
             return self.out
         self.graph.replay()
         return self.out
-
-    def results(self):
-        """Synchronising read-back: list of dict(box3d_lidar, scores, label_preds) numpy per frame; raises on overflow."""
-        cnt = self.out["count"].cpu().numpy()
-        if int(self.err.item()) != 0:
-            self.err.zero_()  # sticky flag: reported once, then re-armed
-            raise RuntimeError("sparse level capacity overflow: raise `growth` or max_voxels")
-        res = []
-        for b in range(self.B):
-            n = int(cnt[b])
-            res.append(dict(box3d_lidar=self.out["box"][b, :n].cpu().numpy(), scores=self.out["score"][b, :n].cpu().numpy(),
-                            label_preds=self.out["label"][b, :n].cpu().numpy().astype(np.int64)))
-        return res

@@ -2651,7 +2651,7 @@ def split_nhwc(y, sizes):
     return SplitNhwcFunction.apply(y, *[int(v) for v in sizes])
 
 
-MAX_TASKS = 4        # multi-task inference: tasks per head (sessd_ssfa_fuse_head_tasks / sessd_predict_tasks)
+MAX_TASKS = 4        # multi-task inference: tasks per head (sessd_ssfa_fuse_head_tasks / sessd_predict)
 TASK_HEAD_CH = 22    # planar head channels of one task: [box 14 | cls 2 | dir 4 | iou 2], one class, two rotations per location
 
 
@@ -2667,7 +2667,7 @@ def ssfa_fuse_head(x0, x1, w0, w1, s0, t0, s1, t1, head_w, head_b, head_out=None
     """ssfa_fuse + the 1x1 heads in one launch: head_w (22, C) row-major, head_b (22) or None -> head_out (B, 22, H*W) planar.
     `out` (B, C, H, W): optional buffer that receives the SSFA output (not written when None).
     keys (B, 2*H*W) int64 + key_count (B,) int32 (zeroed by the caller): the launch also appends predict's score-filter keys
-    (sessd_ssfa_fuse_head_keys) -- the inputs predict_fused() takes instead of running its own score filter.
+    (sessd_ssfa_fuse_head_keys) -- the inputs predict() takes instead of running its own score filter.
     num_tasks = T > 1 (sessd_ssfa_fuse_head_tasks): head_w (T*22, C), head_b (T*22) or None -> head_out (B, T*22, H*W) =
     (B, T, 22, H*W), task t's planes bit-equal to the single-task call with task t's weights; keys (B, T, 2*H*W) and key_count
     (B*T,) per (frame, task)."""
@@ -2743,7 +2743,7 @@ def fill_multi(segments):
 
 # ------------------------------------------------------------------ predict / post-processing
 NMS_TYPES = ("rotate_nms", "rotate_weighted_nms")
-DI_MAX_CANDIDATES = 1024   # sessd_predict_di: one thread per candidate in the selection workgroup
+DI_MAX_CANDIDATES = 1024   # sessd_predict with DI-NMS: one thread per candidate in the selection workgroup
 # the literals get_task_detections passes to rotate_weighted_nms (mg_head_sessd.py:1012-1017)
 DI_DEFAULTS = dict(nms_cnt_thresh=2.6, nms_sigma_dist_interval=(0, 20, 40, 60), nms_sigma_square=(0.0009, 0.009, 0.1, 1),
                    suppressed_thresh=0.3, centerness_pow=2)
@@ -2789,118 +2789,117 @@ def check_di(di, pre_max=None):
     return c
 
 
-def predict(head, anchors, frustum=None, score_thresh=0.3, pre_max=1000, post_max=100, nms_thresh=0.01,
-            post_center_range=(0, -40.0, -5.0, 70.4, 40.0, 5.0), direction_offset=0.0, out=None, keys=None, key_count=None,
-            records=None, num_tasks=1, nms_type="rotate_nms", di=None):
-    """head (B,22,P) planar float32; anchors (A,7) or (B,A,7); frustum (B,1,6,4,3) float64 or None.
-    Returns dict(box (B,post,7), score (B,post), label (B,post) int32, count (B,) int32), all on the device.
-    keys / key_count: the score-filter keys already produced by ssfa_fuse_head(keys=...) (sessd_predict_fused skips its own
-    filter); records = (records (F,post,9) float32, counts (F,) int32, cursor (1,) int32): the call's last launch also appends the
-    frames' detection records to that ring.
-    num_tasks = T > 1 (sessd_predict_tasks): head (B,T*22,P) = (B,T,22,P); anchors (T,A,7) shared by the frames or (B,T,A,7);
-    every task runs its own score filter, top-k, NMS and post_max. Returns box (B,T*post,7), score / label (B,T*post), count (B,)
-    -- task 0's detections in NMS order, then task 1's, ...; label = task index -- and task_count (B,T); records (F,T*post,9).
-    nms_type = "rotate_weighted_nms" (sessd_predict_di, any T): DI-NMS instead of the greedy rotated NMS, per (frame, task), with
-    the settings `di` (keys of DI_DEFAULTS; None = the reference's literals); pre_max <= 1024; nms_thresh is not read (as in the
-    reference). The selection stops at post_max kept boxes: the result also carries di_truncated (B,T) int32, 1 where candidates
-    were left, and di_keep (B,T,post) / di_keep_count (B,T): the kept candidates' ranks in the top-k order before the filters.
-    Returns the layout of num_tasks = T (task_count included) for every T."""
-    if nms_type not in NMS_TYPES:
-        raise ValueError("nms_type must be one of %s, got %r" % (NMS_TYPES, nms_type))
-    di_cfg = check_di({} if di is None else di, pre_max) if nms_type == "rotate_weighted_nms" else None
-    _req(head, torch.float32, "head")
-    _req(anchors, torch.float32, "anchors")
-    B, ch, P = head.shape
-    T = check_num_tasks(num_tasks)
-    if di_cfg is not None:
+def _predict_layout(B, T, post_max, multi, di):
+    """(name, shape, dtype) of predict's outputs. multi: the layout of num_tasks = T > 1 and of DI-NMS, task_count included. di:
+    DI-NMS adds where the selection stopped at post_max with candidates left, the kept candidates' ranks in the top-k order before
+    the filters (the reference's `selected`) and their number."""
+    f32, i32 = torch.float32, torch.int32
+    rows = [("box", (B, T * post_max, 7), f32), ("score", (B, T * post_max), f32), ("label", (B, T * post_max), i32), ("count", (B,), i32)]
+    if multi:
+        rows.append(("task_count", (B, T), i32))
+    if di:
+        rows += [("di_truncated", (B, T), i32), ("di_keep", (B, T, post_max), i32), ("di_keep_count", (B, T), i32)]
+    return rows
+
+
+class Predict:
+    """The predict stage of one shape and one set of settings: validated once, its sessd_predict_args_t filled once, launched many
+    times. B frames, T = num_tasks, P = H * W pixels; anchors (A,7) / (B,A,7) for T = 1, (T,A,7) / (B,T,A,7) for any T, A = 2 * P;
+    frustum (B,1,6,4,3) float64 or None; the settings as predict() documents them.
+    out: preallocated outputs, used as they are (box, score, label, count; task_count, di_truncated, di_keep + di_keep_count where
+    present); None = a fresh dict in predict()'s layout for (T, nms_type). sticky: one int32 that DI-NMS ORs its truncation flag
+    into. workspace: an owned uint8 tensor of at least `need` bytes; None = the cached workspace(need, device, "predict") of the
+    stream and capture scope each launch runs in.
+    The object keeps every tensor alive whose address the struct holds; head, keys and records are bound per launch()."""
+
+    def __init__(self, B, T, P, anchors, frustum=None, score_thresh=0.3, pre_max=1000, post_max=100, nms_thresh=0.01,
+                 post_center_range=(0, -40.0, -5.0, 70.4, 40.0, 5.0), direction_offset=0.0, nms_type="rotate_nms", di=None,
+                 device=None, out=None, workspace=None, sticky=None):
+        from ._lib import PredictArgs
+        if nms_type not in NMS_TYPES:
+            raise ValueError("nms_type must be one of %s, got %r" % (NMS_TYPES, nms_type))
+        self.di_cfg = check_di({} if di is None else di, pre_max) if nms_type == "rotate_weighted_nms" else None
+        _req(anchors, torch.float32, "anchors")
+        B, T, P, post_max = int(B), check_num_tasks(T), int(P), int(post_max)
+        self.B, self.T, self.P, self.post_max = B, T, P, post_max
         if T == 1 and anchors.dim() in (2, 3):  # (A,7) / (B,A,7) -> (1,A,7) / (B,1,A,7)
             anchors = anchors.unsqueeze(-3)
-        return _predict_tasks(head, anchors, frustum, score_thresh, pre_max, post_max, nms_thresh, post_center_range,
-                              direction_offset, out, keys, key_count, records, T, di_cfg)
-    if T > 1:
-        return _predict_tasks(head, anchors, frustum, score_thresh, pre_max, post_max, nms_thresh, post_center_range,
-                              direction_offset, out, keys, key_count, records, T)
-    assert ch == 22
-    per_frame = 0
-    if anchors.dim() == 3:
-        per_frame = anchors.shape[1]
-        assert anchors.shape[0] == B
-    assert anchors.shape[-2] == 2 * P and anchors.shape[-1] == 7
-    if frustum is not None:
-        _req(frustum, torch.float64, "frustum")
-        assert frustum.numel() == B * 72
-    dev = head.device
-    if out is None:
-        out = dict(box=torch.empty((B, post_max, 7), dtype=torch.float32, device=dev),
-                   score=torch.empty((B, post_max), dtype=torch.float32, device=dev),
-                   label=torch.empty((B, post_max), dtype=torch.int32, device=dev),
-                   count=torch.empty((B,), dtype=torch.int32, device=dev))
-    need = lib.sessd_predict_workspace_bytes(B, 2 * P, pre_max, post_max)
-    ws = workspace(need, dev, "predict")
-    rng = torch.tensor(post_center_range, dtype=torch.float32)
-    rec, rcnt, rcur = records if records is not None else (None, None, None)
-    check(lib.sessd_predict_fused(head.data_ptr(), B, P, anchors.data_ptr(), per_frame, _p(frustum), float(score_thresh),
-                                  pre_max, post_max, float(nms_thresh), rng.data_ptr(), float(direction_offset),
-                                  out["box"].data_ptr(), out["score"].data_ptr(), out["label"].data_ptr(),
-                                  out["count"].data_ptr(), _p(keys), _p(key_count), _p(rec), _p(rcnt),
-                                  int(rec.shape[0]) if rec is not None else 0, _p(rcur), ws.data_ptr(), ws.numel(), _stream()),
-          "predict_fused")
-    return out
+        assert anchors.dim() in (3, 4) and tuple(anchors.shape[-3:]) == (T, 2 * P, 7), "anchors: (T, 2*P, 7) or (B, T, 2*P, 7)"
+        assert anchors.dim() == 3 or anchors.shape[0] == B
+        if frustum is not None:
+            _req(frustum, torch.float64, "frustum")
+            assert frustum.numel() == B * 72
+        self.dev = dev = anchors.device if device is None else device
+        multi = T > 1 or self.di_cfg is not None
+        if out is None:
+            out = {name: torch.empty(shape, dtype=dt, device=dev)
+                   for name, shape, dt in _predict_layout(B, T, post_max, multi, self.di_cfg is not None)}
+        assert out["box"].numel() >= B * T * post_max * 7 and out["score"].numel() >= B * T * post_max
+        self.anchors, self.frustum, self.out, self.sticky, self.ws = anchors, frustum, out, sticky, workspace
+        self.need = int(lib.sessd_predict_workspace_bytes(B, T, 2 * P, int(pre_max), post_max, 0 if self.di_cfg is None else 1))
+        assert workspace is None or workspace.numel() >= self.need
+        a = self.args = PredictArgs()
+        a.batch, a.num_tasks, a.num_pixels = B, T, P
+        a.anchors, a.anchors_per_frame, a.frustum = anchors.data_ptr(), 2 * P if anchors.dim() == 4 else 0, _p(frustum)
+        a.score_thresh, a.pre_max_size, a.post_max_size, a.nms_iou_thresh = float(score_thresh), int(pre_max), post_max, float(nms_thresh)
+        a.post_center_range[:] = [float(v) for v in post_center_range]
+        a.direction_offset = float(direction_offset)
+        a.out_box, a.out_score, a.out_label, a.out_count = [out[k].data_ptr() for k in ("box", "score", "label", "count")]
+        a.out_task_count = _p(out.get("task_count")) if multi else 0
+        if self.di_cfg is not None:
+            assert out["di_truncated"].numel() >= B * T and out["di_truncated"].dtype == torch.int32
+            a.di = ctypes.pointer(self.di_cfg)
+            a.di_truncated, a.di_truncated_sticky = out["di_truncated"].data_ptr(), _p(sticky)
+            a.di_keep, a.di_keep_count = _p(out.get("di_keep")), _p(out.get("di_keep_count"))
+
+    def launch(self, head, keys=None, records=None, stream=None):
+        """One call of sessd_predict on head (B, T*22, P). keys = (keys, key_count): the score-filter keys the head launch already
+        produced; records = (records (F, T*post, 9), counts (F,), cursor (1,)): the ring the call's last launch appends the frames'
+        detection records to. None = absent: both bindings are set on EVERY launch, so none survives from an earlier one."""
+        B, T, P, a = self.B, self.T, self.P, self.args
+        _req(head, torch.float32, "head")
+        if tuple(head.shape) != (B, T * TASK_HEAD_CH, P):
+            raise ValueError("predict takes 22 planar head channels per task (one class, two rotations per location): head (%d, %d, %d), "
+                             "got %s for %d tasks" % (B, T * TASK_HEAD_CH, P, tuple(head.shape), T))
+        k, kc = keys if keys is not None else (None, None)
+        if k is not None:
+            assert kc is not None and k.numel() >= B * T * 2 * P and kc.numel() >= B * T
+        rec, rcnt, rcur = records if records is not None else (None, None, None)
+        if rec is not None:
+            assert rec.shape[1] == T * self.post_max and rec.shape[2] == 9, "records: (frames, num_tasks * post_max, 9)"
+        a.head, a.ext_keys, a.ext_key_count = head.data_ptr(), _p(k), _p(kc)
+        a.records, a.record_counts, a.cursor = _p(rec), _p(rcnt), _p(rcur)
+        a.capacity_frames = int(rec.shape[0]) if rec is not None else 0
+        ws = self.ws if self.ws is not None else workspace(self.need, self.dev, "predict")
+        check(lib.sessd_predict(ctypes.byref(a), ws.data_ptr(), ws.numel(), _stream() if stream is None else stream), "predict")
+        return self.out
 
 
-def _predict_tasks(head, anchors, frustum, score_thresh, pre_max, post_max, nms_thresh, post_center_range, direction_offset, out,
-                   keys, key_count, records, T, di_cfg=None):
-    B, ch, P = head.shape
-    if ch != T * TASK_HEAD_CH:
-        raise ValueError("multi-task predict takes 22 planar head channels per task (one class, two rotations per location): "
-                         "%d channels for %d tasks" % (ch, T))
-    per_frame = 0
-    if anchors.dim() == 4:
-        per_frame = anchors.shape[2]
-        assert anchors.shape[0] == B
-    assert anchors.dim() in (3, 4) and tuple(anchors.shape[-3:]) == (T, 2 * P, 7), "anchors: (T, 2*P, 7) or (B, T, 2*P, 7)"
-    if frustum is not None:
-        _req(frustum, torch.float64, "frustum")
-        assert frustum.numel() == B * 72
-    dev = head.device
-    if out is None:
-        out = dict(box=torch.empty((B, T * post_max, 7), dtype=torch.float32, device=dev),
-                   score=torch.empty((B, T * post_max), dtype=torch.float32, device=dev),
-                   label=torch.empty((B, T * post_max), dtype=torch.int32, device=dev),
-                   count=torch.empty((B,), dtype=torch.int32, device=dev),
-                   task_count=torch.empty((B, T), dtype=torch.int32, device=dev))
-    assert out["box"].numel() >= B * T * post_max * 7 and out["score"].numel() >= B * T * post_max
-    if keys is not None:
-        assert key_count is not None and keys.numel() >= B * T * 2 * P and key_count.numel() >= B * T
-    rng = torch.tensor(post_center_range, dtype=torch.float32)
-    rec, rcnt, rcur = records if records is not None else (None, None, None)
-    if rec is not None:
-        assert rec.shape[1] == T * post_max and rec.shape[2] == 9, "records: (frames, num_tasks * post_max, 9)"
-    if di_cfg is not None:
-        import ctypes
-        if "di_truncated" not in out:
-            out["di_truncated"] = torch.empty((B, T), dtype=torch.int32, device=dev)
-        assert out["di_truncated"].numel() >= B * T and out["di_truncated"].dtype == torch.int32
-        if "di_keep" not in out:  # the kept candidates' ranks before the filters (the reference's `selected`) and their number
-            out["di_keep"] = torch.empty((B, T, post_max), dtype=torch.int32, device=dev)
-            out["di_keep_count"] = torch.empty((B, T), dtype=torch.int32, device=dev)
-        ws = workspace(lib.sessd_predict_di_workspace_bytes(B, T, 2 * P, pre_max, post_max), dev, "predict")
-        check(lib.sessd_predict_di(head.data_ptr(), B, T, P, anchors.data_ptr(), per_frame, _p(frustum), float(score_thresh),
-                                   pre_max, post_max, float(nms_thresh), rng.data_ptr(), float(direction_offset),
-                                   out["box"].data_ptr(), out["score"].data_ptr(), out["label"].data_ptr(),
-                                   out["count"].data_ptr(), _p(out.get("task_count")), _p(keys), _p(key_count), _p(rec), _p(rcnt),
-                                   int(rec.shape[0]) if rec is not None else 0, _p(rcur), ctypes.addressof(di_cfg),
-                                   out["di_truncated"].data_ptr(), _p(out.get("di_truncated_sticky")), out["di_keep"].data_ptr(),
-                                   out["di_keep_count"].data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "predict_di")
-        return out
-    ws = workspace(lib.sessd_predict_tasks_workspace_bytes(B, T, 2 * P, pre_max, post_max), dev, "predict")
-    check(lib.sessd_predict_tasks(head.data_ptr(), B, T, P, anchors.data_ptr(), per_frame, _p(frustum), float(score_thresh),
-                                  pre_max, post_max, float(nms_thresh), rng.data_ptr(), float(direction_offset),
-                                  out["box"].data_ptr(), out["score"].data_ptr(), out["label"].data_ptr(),
-                                  out["count"].data_ptr(), _p(out.get("task_count")), _p(keys), _p(key_count), _p(rec), _p(rcnt),
-                                  int(rec.shape[0]) if rec is not None else 0, _p(rcur), ws.data_ptr(), ws.numel(), _stream()),
-          "predict_tasks")
-    return out
+def predict(head, anchors, frustum=None, score_thresh=0.3, pre_max=1000, post_max=100, nms_thresh=0.01,
+            post_center_range=(0, -40.0, -5.0, 70.4, 40.0, 5.0), direction_offset=0.0, out=None, keys=None, key_count=None,
+            records=None, num_tasks=1, nms_type="rotate_nms", di=None, sticky=None):
+    """head (B,22,P) planar float32; anchors (A,7) or (B,A,7); frustum (B,1,6,4,3) float64 or None.
+    Returns dict(box (B,post,7), score (B,post), label (B,post) int32, count (B,) int32), all on the device.
+    keys / key_count: the score-filter keys already produced by ssfa_fuse_head(keys=...) (sessd_predict skips its own filter);
+    records = (records (F,post,9) float32, counts (F,) int32, cursor (1,) int32): the call's last launch also appends the
+    frames' detection records to that ring.
+    num_tasks = T > 1: head (B,T*22,P) = (B,T,22,P); anchors (T,A,7) shared by the frames or (B,T,A,7);
+    every task runs its own score filter, top-k, NMS and post_max. Returns box (B,T*post,7), score / label (B,T*post), count (B,)
+    -- task 0's detections in NMS order, then task 1's, ...; label = task index -- and task_count (B,T); records (F,T*post,9).
+    nms_type = "rotate_weighted_nms" (any T): DI-NMS instead of the greedy rotated NMS, per (frame, task), with
+    the settings `di` (keys of DI_DEFAULTS; None = the reference's literals); pre_max <= 1024; nms_thresh is not read (as in the
+    reference). The selection stops at post_max kept boxes: the result also carries di_truncated (B,T) int32, 1 where candidates
+    were left (sticky: one int32 that 1 is ORed into in that case), and di_keep (B,T,post) / di_keep_count (B,T): the kept
+    candidates' ranks in the top-k order before the filters. Returns the layout of num_tasks = T (task_count included) for every T.
+    One Predict built and launched once: a caller with a fixed shape keeps the Predict instead."""
+    B, _, P = head.shape
+    if out is not None and nms_type == "rotate_weighted_nms":  # a caller's dict receives the DI entries it lacks
+        for name, shape, dt in _predict_layout(B, check_num_tasks(num_tasks), post_max, True, True):
+            if name.startswith("di_") and name not in out:
+                out[name] = torch.empty(shape, dtype=dt, device=head.device)
+    stage = Predict(B, num_tasks, P, anchors, frustum, score_thresh, pre_max, post_max, nms_thresh, post_center_range, direction_offset,
+                    nms_type, di, head.device, out, sticky=sticky)
+    return stage.launch(head, None if keys is None else (keys, key_count), records)
 
 
 def rotate_nms_corners_sorted(corners, thresh, post_max):

@@ -28,7 +28,7 @@ from torch import nn
 
 from ._lib import lib, check
 from . import ops
-from .engine import fold_bn, _round_up
+from .engine import FrameEngine, fold_bn, _round_up
 
 UP_STRIDES = (1, 2, 4)   # sessd_deconv_ks_slice
 FRONT_ENDS = ("fused", "tensor")
@@ -128,7 +128,7 @@ def check_pillar_model(model, canvas_hw=None):
     return dict(blocks=blocks, ups=ups, head=t)
 
 
-class PillarEngine:
+class PillarEngine(FrameEngine):
     num_tasks = 1   # one head task (check_pillar_model): a frame's record holds post_max rows
 
     def __init__(self, model, voxel_generator_cfg, test_cfg, batch_size=1, max_points=32768, anchors=None, device=None,
@@ -235,24 +235,15 @@ class PillarEngine:
                             di_keep=torch.zeros((B, 1, post), dtype=i32, device=dev), di_keep_count=torch.zeros((B, 1), dtype=i32, device=dev))
         # the STICKY OR of DI-NMS's di_truncated over all frames so far (outside every per-frame clear, like self.err; nothing raises)
         self.nms_truncated = torch.zeros((1,), dtype=i32, device=dev)
-        self._pred_out = dict(self.out, di_truncated_sticky=self.nms_truncated) if self.nms_type == "rotate_weighted_nms" else self.out
+        self.pred_ws = torch.empty(int(lib.sessd_predict_workspace_bytes(B, 1, 2 * H * W, self.pre_max, post, 0 if self.di is None else 1)),
+                                   dtype=torch.uint8, device=dev)
+        self.predict = ops.Predict(B, 1, H * W, self.anchors, None, self.score_thresh, self.pre_max, post, self.nms_thresh, self.post_range,
+                                   self.dir_offset, self.nms_type, self.di, dev, out=self.out, workspace=self.pred_ws,
+                                   sticky=self.nms_truncated)
         # compute units this engine's stream may use (0 = the whole chip): sizes the persistent launches of ops.conv2d
         self.cu_budget = 0
-        self.records = self.record_counts = self.record_cursor = None
         self.graph = None
         self._marks = None
-
-    def attach_records(self, capacity_frames):
-        """Keep every frame's detections on the device as a fixed-size record (capacity_frames, post_max, 9) [box 7 | score | label]
-        + counts, appended by the frame's own last launch (also inside a captured graph, hence before capture())."""
-        if self.graph is not None:
-            raise RuntimeError("attach_records must precede capture(): the ring's address is baked into the graph")
-        cap = max(int(capacity_frames), self.B)
-        f32, i32 = torch.float32, torch.int32
-        self.records = torch.zeros((cap, self.post_max, 9), dtype=f32, device=self.dev)
-        self.record_counts = torch.zeros((cap,), dtype=i32, device=self.dev)
-        self.record_cursor = torch.zeros((1,), dtype=i32, device=self.dev)
-        return self.records, self.record_counts
 
     def _wgs(self):
         """persistent workgroups of a stream-K launch of ops.conv2d (InferenceEngine._wgs): 0 = the library's choice for the whole chip"""
@@ -352,9 +343,7 @@ class PillarEngine:
                    workgroups=wgs)
         self._mark("head")
         # ---- 6. predict
-        ops.predict(self.head, self.anchors, None, self.score_thresh, self.pre_max, self.post_max, self.nms_thresh, self.post_range,
-                    self.dir_offset, out=self._pred_out, nms_type=self.nms_type, di=self.di,
-                    records=None if self.records is None else (self.records, self.record_counts, self.record_cursor))
+        self.predict.launch(self.head, records=self._record_ring(), stream=s)
         self._mark("predict")
         return self.out
 
@@ -397,17 +386,3 @@ class PillarEngine:
     def replay(self):
         self.graph.replay()
         return self.out
-
-    def results(self):
-        """The one synchronising read-back: list of dict(box3d_lidar, scores, label_preds) numpy per frame; raises (once, then
-        re-armed) when a pillar fell outside the canvas."""
-        cnt = self.out["count"].cpu().numpy()
-        if int(self.err.item()) != 0:
-            self.err.zero_()
-            raise RuntimeError(self.err_text)
-        res = []
-        for b in range(self.B):
-            n = int(cnt[b])
-            res.append(dict(box3d_lidar=self.out["box"][b, :n].cpu().numpy(), scores=self.out["score"][b, :n].cpu().numpy(),
-                            label_preds=self.out["label"][b, :n].cpu().numpy().astype(np.int64)))
-        return res

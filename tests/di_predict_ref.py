@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE ONLY -- numpy restatement of get_task_detections with nms_type = 'rotate_weighted_nms' (DI-NMS) for ONE
-(frame, task), the CPU reference of sessd_predict_di / ops.predict(nms_type="rotate_weighted_nms").
+(frame, task), the CPU reference of sessd_predict with args->di / ops.predict(nms_type="rotate_weighted_nms").
 
 Follows, line by line:
   det3d/models/bbox_heads/mg_head_sessd.py:955-982    sigmoid, >= thresh, iou_preds = (iou + 1) / 2, score *= iou_preds^4

@@ -176,3 +176,44 @@ def test_head_loss_entry_point_checks_its_arguments():
     assert lib.sessd_head_loss(None, None, None, None, None, None, None, None, None, None, None, None, 0, None) == -1
     c.batch = 65
     assert lib.sessd_head_loss_workspace_bytes(C.addressof(c)) == 0
+
+
+def test_predict_args_mirror_and_argument_checks():
+    """sessd_predict_args_t and _lib.PredictArgs are one layout: the same size as the library compiled it, the same fields in the
+    same order, pointer for pointer and scalar for scalar. The entry point's argument checks come before any device call (null
+    pointers, no GPU): SESSD_EINVAL = -1, SESSD_EWORKSPACE = -2; the workspace query returns 0 for what it refuses."""
+    import ctypes
+    import sessd_hip
+    from sessd_hip._lib import DiCfg, PredictArgs
+    lib = sessd_hip.lib
+    assert ctypes.sizeof(PredictArgs) == lib.sessd_predict_args_bytes()
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sessd_hip_types.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct \{([^}]*)\} sessd_predict_args_t;", txt).group(1)
+    decls = [re.fullmatch(r"(const\s+)?(\w+)\s*(\*?)\s*(\w+)(\[(\d+)\])?", d.strip()).groups() for d in body.split(";") if d.strip()]
+    scalar = dict(int32_t=ctypes.c_int, float=ctypes.c_float)
+    assert len(decls) == len(PredictArgs._fields_) == 29
+    for (_, ctype, star, name, _, dim), (pname, ptype) in zip(decls, PredictArgs._fields_):
+        assert name == pname
+        if star:
+            assert ptype is ctypes.c_void_p or (ctype == "sessd_di_cfg_t" and ptype is ctypes.POINTER(DiCfg)), name
+        else:
+            assert ptype is (scalar[ctype] * int(dim) if dim else scalar[ctype]), name
+
+    def call(**kw):
+        v = dict(batch=1, num_tasks=1, num_pixels=64, score_thresh=0.3, pre_max_size=100, post_max_size=10, nms_iou_thresh=0.01)
+        v.update(kw)
+        return lib.sessd_predict(PredictArgs(**v), None, 0, None)
+
+    di = DiCfg(n_interval=4)
+    assert lib.sessd_predict(None, None, 0, None) == -1
+    assert call() == -2 and call(di=ctypes.pointer(di)) == -2          # valid scalars: every check passes, no workspace given
+    assert call(num_tasks=0) == -1 and call(num_tasks=5) == -1
+    assert call(batch=0) == -1 and call(num_pixels=0) == -1 and call(post_max_size=0) == -1 and call(pre_max_size=1985) == -1
+    assert call(pre_max_size=1025) == -2 and call(pre_max_size=1025, di=ctypes.pointer(di)) == -1
+    assert call(di=ctypes.pointer(DiCfg(n_interval=9))) == -1 and call(di=ctypes.pointer(DiCfg(n_interval=-1))) == -1
+    assert call(ext_keys=16) == -1 and call(ext_key_count=16) == -1 and call(di_keep=16) == -1   # both or neither
+    assert call(records=16) == -1 and call(records=16, record_counts=16, cursor=16, capacity_frames=0) == -1
+    assert call(anchors_per_frame=64) == -1 and call(anchors_per_frame=128) == -2
+    wb = lib.sessd_predict_workspace_bytes
+    assert wb(0, 1, 128, 100, 10, 0) == 0 and wb(1, 0, 128, 100, 10, 0) == 0 and wb(1, 5, 128, 100, 10, 1) == 0
+    assert wb(1, 1, 128, 1025, 10, 1) == 0 and wb(1, 1, 128, 0, 10, 1) == 0 and wb(1, 1, 128, 1025, 10, 0) > 0

@@ -82,19 +82,26 @@ def test_unknown_nms_type_and_too_many_candidates_raise_before_any_device_call()
 
 def test_c_entry_points_check_their_arguments():
     import sessd_hip
-    from sessd_hip._lib import DiCfg
+    from sessd_hip._lib import DiCfg, PredictArgs
     lib = sessd_hip.lib
-    wb = lib.sessd_predict_di_workspace_bytes
+    wb = lambda *v: lib.sessd_predict_workspace_bytes(*v, 1)
     assert wb(1, 1, 128, 1025, 10) == 0 and wb(1, 5, 128, 100, 10) == 0 and wb(0, 1, 128, 100, 10) == 0
     # the dense overlap matrices are counted: (pre_max, pre_max) float32 per virtual frame
     assert wb(2, 3, 5120, 1000, 100) >= 6 * 1000 * 1000 * 4 and wb(1, 1, 5120, 1000, 100) - wb(1, 1, 5120, 500, 100) >= 3 * 10 ** 6
     c = DiCfg()
     c.n_interval = 4
-    call = lambda cfg, pre, nt=1: lib.sessd_predict_di(None, 1, nt, 64, None, 0, None, 0.3, pre, 10, 0.01, None, 0.0, None, None, None,
-                                                        None, None, None, None, None, None, 0, None, cfg, None, None, None, None, None, 0, None)
-    assert call(None, 100) == -1 and call(ctypes.addressof(c), 1025) == -1 and call(ctypes.addressof(c), 100, nt=5) == -1
-    c.n_interval = 9
-    assert call(ctypes.addressof(c), 100) == -1
+
+    def call(pre, nt=1):
+        args = PredictArgs(batch=1, num_tasks=nt, num_pixels=64, score_thresh=0.3, pre_max_size=pre, post_max_size=10, nms_iou_thresh=0.01,
+                           di=ctypes.pointer(c))
+        return lib.sessd_predict(args, None, 0, None)
+
+    assert call(1025) == -1 and call(100, nt=5) == -1
+    assert call(100) == -2   # valid settings pass every argument check and stop at the workspace (none given)
+    # DI requested without a usable config: n_interval out of range (a NULL `di` selects the greedy NMS)
+    for bad in (9, -1):
+        c.n_interval = bad
+        assert call(100) == -1
 
 
 def test_configs():

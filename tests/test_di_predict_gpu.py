@@ -1,4 +1,4 @@
-"""DI-NMS as the post-processor of the fused predict call (sessd_predict_di, ops.predict(nms_type="rotate_weighted_nms")) at
+"""DI-NMS as the post-processor of the fused predict call (sessd_predict with args->di, ops.predict(nms_type="rotate_weighted_nms")) at
 kernel level, per (frame, task), against the CPU helper tests/di_predict_ref.py, on the 40 x 32 map, the `_task_head` recipe and
 the TASK_ANCHORS of tests/test_multitask_head_gpu.py (2560 anchors per task), B = 2, T in {1, 3}.
 
@@ -83,10 +83,8 @@ def _call(dev, name, cnt, pre_max, post_max, use_frustum, records=None, sticky=N
                label=torch.full((B, T * post_max), -9, dtype=torch.int32, device=dev),
                count=torch.full((B,), -1, dtype=torch.int32, device=dev), task_count=torch.full((B, T), -1, dtype=torch.int32, device=dev),
                di_truncated=torch.full((B, T), -1, dtype=torch.int32, device=dev))
-    if sticky is not None:
-        out["di_truncated_sticky"] = sticky
     ops.predict(head, anchors, fr, 0.3, pre_max, post_max, 0.01, out=out, records=records, num_tasks=T, nms_type=DI,
-                di=dict(nms_cnt_thresh=cnt), **kw)
+                di=dict(nms_cnt_thresh=cnt), sticky=sticky, **kw)
     return head, anchors, fr, out
 
 

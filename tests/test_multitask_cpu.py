@@ -82,14 +82,16 @@ def test_limits_raise_value_errors_that_name_them():
 
 
 def test_c_entry_points_reject_task_counts_before_touching_the_device():
+    from sessd_hip._lib import PredictArgs
     lib = ops.lib
     for nt in (0, 5):
         assert lib.sessd_ssfa_fuse_head_tasks(None, None, None, None, 1.0, 0.0, 1.0, 0.0, 1, 128, 64, None, None, None, nt, None, 0.0,
                                               None, 0, None, None) == -1
-        assert lib.sessd_predict_tasks(None, 1, nt, 64, None, 0, None, 0.3, 100, 10, 0.01, None, 0.0, None, None, None, None, None, None,
-                                       None, None, None, 0, None, None, 0, None) == -1
-        assert lib.sessd_predict_tasks_workspace_bytes(1, nt, 128, 100, 10) == 0
-    # one task: the workspace of before; more tasks: per (frame, task) plus the rows the merge reads
-    one = lib.sessd_predict_workspace_bytes(2, 128, 100, 10)
-    assert lib.sessd_predict_tasks_workspace_bytes(2, 1, 128, 100, 10) == one
-    assert lib.sessd_predict_tasks_workspace_bytes(2, 3, 128, 100, 10) > lib.sessd_predict_workspace_bytes(6, 128, 100, 10)
+        args = PredictArgs(batch=1, num_tasks=nt, num_pixels=64, score_thresh=0.3, pre_max_size=100, post_max_size=10, nms_iou_thresh=0.01)
+        assert lib.sessd_predict(args, None, 0, None) == -1
+        assert lib.sessd_predict_workspace_bytes(1, nt, 128, 100, 10, 0) == 0
+    # one task: the workspace of before (64000 bytes: what the single-task query returned for these arguments while it was a
+    # function of its own); more tasks: per (frame, task) plus the rows the merge reads
+    one = 64000
+    assert lib.sessd_predict_workspace_bytes(2, 1, 128, 100, 10, 0) == one
+    assert lib.sessd_predict_workspace_bytes(2, 3, 128, 100, 10, 0) > lib.sessd_predict_workspace_bytes(6, 1, 128, 100, 10, 0)

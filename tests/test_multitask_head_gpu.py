@@ -1,4 +1,4 @@
-"""Multi-task heads at kernel level: sessd_ssfa_fuse_head_tasks and sessd_predict_tasks (ops.ssfa_fuse_head / ops.predict with
+"""Multi-task heads at kernel level: sessd_ssfa_fuse_head_tasks and sessd_predict (ops.ssfa_fuse_head / ops.predict with
 num_tasks > 1) against the single-task entry points (bit for bit), a float64 restatement and the CPU oracle.
 
 Tolerances are the existing tests' own: head planes within 2e-5 * max(1, |ref|max) of float64 (tests/test_dense_conv_gpu.py::

@@ -99,7 +99,7 @@ def test_rotate_nms_sorted_vs_oracle(dev, n, thresh):
 
 
 def test_fused_forms_equal_the_plain_call(dev):
-    """sessd_predict_fused's two optional fusions give what the separate launches give, bit for bit:
+    """sessd_predict's two optional fusions give what the separate launches give, bit for bit:
     * the score-filter keys produced INSIDE the head launch (sessd_ssfa_fuse_head_keys) -- same detections as the call that
       filters the stored head tensor itself, and the same KEY SET as score_filter_kernel would append;
     * the frame's detection record written by the call's last launch == sessd_pack_detections of the outputs (ring rule:
@@ -145,6 +145,81 @@ def test_fused_forms_equal_the_plain_call(dev):
             r = rec[slot].cpu()
             assert torch.equal(r[:n, :7], plain["box"][b, :n].cpu()) and torch.equal(r[:n, 7], plain["score"][b, :n].cpu())
             assert float(r[:n, 8].abs().max()) == 0 and float(r[n:].abs().max()) == 0
+
+
+def _valid_rows_equal(got, want, B, T):
+    """two predict results, bit for bit in every row a caller may read (rows past a count are never written)"""
+    assert set(got) == set(want)
+    for k in set(got) - {"box", "score", "label", "di_keep"}:        # count, task_count, di_truncated, di_keep_count
+        assert torch.equal(got[k], want[k]), k
+    for b in range(B):
+        n = int(want["count"][b].item())
+        for k in ("box", "score", "label"):
+            assert torch.equal(got[k][b, :n], want[k][b, :n]), (b, k)
+        for t in range(T if "di_keep" in want else 0):
+            n = int(want["di_keep_count"][b, t].item())
+            assert torch.equal(got["di_keep"][b, t, :n], want["di_keep"][b, t, :n]), (b, t)
+
+
+@pytest.mark.parametrize("T,nms_type,pre_max", [(1, "rotate_nms", 64), (3, "rotate_nms", 64), (1, "rotate_weighted_nms", 64),
+                                                (3, "rotate_weighted_nms", 64), (1, "rotate_nms", 1300)])
+def test_one_predict_object_launched_three_times(dev, T, nms_type, pre_max):
+    """One ops.Predict on one head, launched with keys and records bound, then with neither, then with records only: every launch
+    == a fresh ops.predict call with the same bindings, bit for bit -- a binding of an earlier launch never reaches a later one
+    (the key counts are zeroed after launch 1: a stale key binding would find no candidate; the ring is compared around launch 2).
+    Shapes: 10 x 14 pixels (280 anchors per task), B = 2, the seeded head of tests/test_rpn_head_gpu.py whose bias lets a few per
+    cent of the anchors pass; post_max 8; pre_max 1300: the suppression mask does not fit the LDS, the record is written by
+    pack_detections_kernel. A ring of 3 slots: launch 1 takes slots 0, 1, launch 3 wraps into 2, 0."""
+    from sessd_hip import configs
+    from test_rpn_head_gpu import B, _inputs, _ref
+    Hs, Ws, post = 10, 14, 8
+    P = Hs * Ws
+    x, up_w, scale, shift, hw, hb = _inputs(T, Hs, Ws, seed=7)
+    _, _, head0 = _ref(x, up_w, scale, shift, hw, None)
+    hb = hb.clone()
+    for t in range(T):   # per task: the 0.95 quantile of its cls logits lands on the 0.3 score threshold
+        q = float(torch.quantile(head0[:, t * 22 + 14:t * 22 + 16].reshape(-1), 0.95))
+        hb[t * 22 + 14:t * 22 + 16] = float(np.log(0.3 / 0.7)) - q
+        hb[t * 22 + 20:t * 22 + 22] = 0.5
+    d = lambda v: v.to(dev)
+    keys = torch.zeros((B, T, 2 * P), dtype=torch.int64, device=dev)
+    kcnt = torch.zeros((B * T,), dtype=torch.int32, device=dev)
+    head = ops.rpn_up_head(d(x), d(up_w), d(scale), d(shift), d(hw), d(hb), score_thresh=0.3, keys=keys, key_count=kcnt, num_tasks=T)
+    assert int(kcnt.min().item()) > 0
+    anchors = torch.from_numpy(np.ascontiguousarray(configs.kitti_3class_anchors((Hs, Ws), [0, -4.0, -3.0, 5.6, 4.0, 1.0]))).float()[:T]
+    anc = d(anchors if T > 1 else anchors[0])
+    di = dict(nms_cnt_thresh=0.8) if nms_type == "rotate_weighted_nms" else None   # the seeded heads cannot reach the default 2.6
+    cap = 3
+    ring = lambda: (torch.full((cap, T * post, 9), -7.0, device=dev), torch.full((cap,), -1, dtype=torch.int32, device=dev),
+                    torch.zeros((1,), dtype=torch.int32, device=dev))
+    mine, theirs = ring(), ring()   # the object's ring and the fresh calls'
+    stage = ops.Predict(B, T, P, anc, None, 0.3, pre_max, post, 0.01, nms_type=nms_type, di=di, device=dev)
+    cursor = 0
+    for launch, (with_keys, with_rec) in enumerate([(True, True), (False, False), (False, True)]):
+        ring_before = [v.clone() for v in mine]
+        out = stage.launch(head, keys=(keys, kcnt) if with_keys else None, records=mine if with_rec else None)
+        fresh = ops.predict(head, anc, None, 0.3, pre_max, post, 0.01, keys=keys if with_keys else None,
+                            key_count=kcnt if with_keys else None, records=theirs if with_rec else None, num_tasks=T, nms_type=nms_type,
+                            di=di)
+        assert out is stage.out
+        _valid_rows_equal(out, fresh, B, T)
+        count = out["count"].cpu()
+        print("launch", launch, "count", count.tolist(), "keys", kcnt.tolist())
+        if nms_type == "rotate_nms":
+            assert int(count.min()) > 0
+        if not with_rec:     # the ring of launch 1 is not touched
+            assert all(torch.equal(a, b) for a, b in zip(mine, ring_before))
+        else:
+            for b in range(B):
+                slot = (cursor + b) % cap
+                n = int(count[b])
+                r = mine[0][slot]
+                assert int(mine[1][slot].item()) == n and torch.equal(r, theirs[0][slot])
+                assert torch.equal(r[:n, :7], out["box"][b, :n]) and torch.equal(r[:n, 7], out["score"][b, :n])
+                assert torch.equal(r[:n, 8], out["label"][b, :n].float()) and bool((r[n:] == 0).all())
+            cursor += B
+        assert int(mine[2].item()) == cursor == int(theirs[2].item())
+        kcnt.zero_()         # from here on a launch that still read the keys of launch 1 would find no candidate
 
 
 def test_fill_multi(dev):

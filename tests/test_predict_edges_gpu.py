@@ -190,7 +190,7 @@ def test_workspace_reuse_after_another_pre_max(dev, anchors_dev):
     """The cached "predict" workspace holds another layout's bytes (here: all ones, then a pre_max 1000 call's mask) when the
     pre_max 65 call runs: every word a call reads it must have written itself."""
     first, then = pc.REUSE
-    need = ops.lib.sessd_predict_workspace_bytes(1, pc.A, first["pre_max"], first["post_max"])
+    need = ops.lib.sessd_predict_workspace_bytes(1, 1, pc.A, first["pre_max"], first["post_max"], 0)
     ws = ops.workspace(need, dev, "predict")
     ws.fill_(0xFF)
     out1 = _predict(dev, first, anchors_dev)

@@ -63,7 +63,7 @@ def test_rpn_up_head_against_float64(dev, T, H, W, with_bias, with_out):
 @pytest.mark.gpu
 @pytest.mark.parametrize("T", [1, 3])
 def test_launch_keys_equal_predicts_own_score_filter(dev, T):
-    """A cls bias that lets a few per cent of the anchors pass: sessd_predict_tasks (T = 3) / sessd_predict_fused (T = 1) fed the
+    """A cls bias that lets a few per cent of the anchors pass: sessd_predict (T = 3 and T = 1) fed the
     launch's keys == the same call with keys = NULL (its own score filter over the same head tensor), bit for bit."""
     H, W = 10, 14
     P = H * W

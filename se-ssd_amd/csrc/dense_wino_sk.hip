@@ -35,6 +35,10 @@
 //   V : lane (tile j, row pair h) of wave w loads rows (P, Q, S) = (0, 2, 1) / (2, 1, 3) of BOTH channels of k-step w, forms
 //       transform rows 2h (P - Q) and 2h + 1 (Q +- S) -- the f32 transform's values, bit for bit -- and writes the split channel
 //       pairs as 32-bit words into LDS [plane 3][xi 16][channel half 2][tile 32][8 channels] (48 KB per buffer).
+//       The transform of round rr + 1 runs INSIDE round rr: patches loaded at the top of the round, the transform cut into pieces
+//       that stand in the MFMA gaps of steps 3 .. 7 (scalar adds; SESSD_SS_ROUND_PIPE). As one block at the end of the round
+//       (SESSD_WINO_VAR=4, the loop before) both waves of a SIMD ran its ~120 vector instructions together while the matrix pipe
+//       had nothing to issue: 52 -> 47 us for a 256-channel list launch (profiles/wino_split_pipe_*), same bits.
 //   MFMA order per accumulator and round, smallest terms first: a2b0, a1b1, a0b2, a1b0, a0b1, a0b0.
 #include <cstdlib>
 #include "common.hpp"
@@ -66,6 +70,17 @@ __device__ __forceinline__ float sadd(float a, float b) {
   asm volatile("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
+// the same for a - b and for a * b + c (one rounding): the pieces of the split loop's pipelined patch transform
+__device__ __forceinline__ float ssub(float a, float b) {
+  float r;
+  asm volatile("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ float sfma(float a, float b, float c) {
+  float r;
+  asm volatile("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
 
 // the three-way bf16 split of an operand pair (bf16_split.hpp; shared with dense_deconv_split.hip)
 using sessd::pk_bf16;
@@ -93,12 +108,14 @@ struct WinoArgs {
 
 // VAR: measured code variants of the main loop (same arithmetic, same results; `SESSD_WINO_VAR` selects one at launch for
 // A/B runs, 0 ships): bit 0 = the patch transform with scalar adds instead of packed v_pk_add_f32 (MI355X_MICROARCH.md
-// measures packed adds beside MFMAs as an anti-lever), bit 1 = s_setprio around the MFMA groups.
+// measures packed adds beside MFMAs as an anti-lever), bit 1 = s_setprio around the MFMA groups; SPLIT only: bit 2 = the patch
+// transform as one block at the end of the round (the loop before the transform was pipelined into the round's MFMA gaps).
 template <int NW, int CBN, int VAR = 0, bool LIST = false, bool SPLIT = false>
 __global__ __launch_bounds__(NW * 64, 8 / NW) void conv3x3s1_winograd_sk_kernel(WinoArgs A) {
   constexpr int XW = 16 / NW;                          // transform points per wave
   static_assert(XW * CBN == 8, "8 accumulators per wave");
-  static_assert(!SPLIT || (NW == 8 && VAR == 0), "the split main loop is written for 8 waves (a round = one K = 16 MFMA)");
+  static_assert(!SPLIT || (NW == 8 && (VAR & 3) == 0), "the split main loop is written for 8 waves (a round = one K = 16 MFMA)");
+  static_assert(SPLIT || (VAR & 4) == 0, "variant bit 2 belongs to the split main loop");
   constexpr int VBUF_S = 3 * 16 * 64 * 4;              // SPLIT: floats of one V buffer, [plane 3][xi 16][lane 64][8 bf16]
   constexpr int NT = NW * 64;
   constexpr unsigned WSTEP = NW * 2u * 32u * 32u;      // bytes of packed U per k-step
@@ -460,6 +477,101 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void conv3x3s1_winograd_sk_kernel(
     voff ^= VBUF_S;                                                                                \
     ++rr;                                                                                          \
   }
+  // ---- the PIPELINED round (VAR bit 2 clear; ships): the patches of the next round are loaded at the top of the round -- they are
+  // older than the U loads step 3 waits for, so they have landed by then without a wait of their own -- and SESSD_SS_TRANSFORM is cut
+  // into pieces that stand one per MFMA gap of steps 3 .. 7, between sched_barrier(0) fences: the row combinations and the edge
+  // masks in step 3, the column combinations in step 4, then three gaps per element (first term and residual, second term and
+  // residual, third term and the three LDS words). Scalar adds (sadd / ssub / sfma: the same IEEE operations in the same
+  // association as the packed ones of SESSD_SS_TRANSFORM, so V is the same bit for bit). The pieces write the other V buffer, last
+  // read before the previous round's barrier; the round's one barrier follows the last LDS write.
+  // the edge masks select columns, the row combinations add within a column: masking the two combined rows equals combining the
+  // three masked rows (a masked-out column is 0 - 0 or 0 + -0 = +0 either way), at 4 vectors instead of 6 -- and without the
+  // branch on `edge`, which would split the step's MFMA chain over two blocks
+#define SESSD_SS_F_MASK(R, C)                                                                      \
+  {                                                                                                \
+    const f32x4v p = R[C];                                                                         \
+    R[C].x = mask_l ? 0.f : p.x; R[C].y = mask_l ? p.x : p.y;                                      \
+    R[C].z = mask_l ? p.y : p.z; R[C].w = mask_l ? p.z : (mask_r ? 0.f : p.w);                     \
+  }
+#define SESSD_SS_F_ROWA(C)                                                                         \
+  {                                                                                                \
+    ra[C].x = ssub(ps[C][0].x, ps[C][1].x); ra[C].y = ssub(ps[C][0].y, ps[C][1].y);                \
+    ra[C].z = ssub(ps[C][0].z, ps[C][1].z); ra[C].w = ssub(ps[C][0].w, ps[C][1].w);                \
+  }
+  // Q + (h ? -S : S) as one fma with sgn = -1 / 1: the product is exact, the one rounding is the add's
+#define SESSD_SS_F_ROWB(C)                                                                         \
+  {                                                                                                \
+    rb[C].x = sfma(ps[C][2].x, sgn, ps[C][1].x); rb[C].y = sfma(ps[C][2].y, sgn, ps[C][1].y);      \
+    rb[C].z = sfma(ps[C][2].z, sgn, ps[C][1].z); rb[C].w = sfma(ps[C][2].w, sgn, ps[C][1].w);      \
+  }
+#define SESSD_SS_F_COLS(C, R, O)                                                                   \
+  {                                                                                                \
+    vt[C][(O) + 0] = ssub(R[C].x, R[C].z); vt[C][(O) + 1] = sadd(R[C].y, R[C].z);                  \
+    vt[C][(O) + 2] = ssub(R[C].z, R[C].y); vt[C][(O) + 3] = ssub(R[C].y, R[C].w);                  \
+  }
+  // split3_pk (bf16_split.hpp) of element E in three pieces
+#define SESSD_SS_F_TERM(T, E)                                                                      \
+  {                                                                                                \
+    T = pk_bf16(vt[0][E], vt[1][E]);                                                               \
+    vt[0][E] = ssub(vt[0][E], __builtin_bit_cast(float, T << 16));                                 \
+    vt[1][E] = ssub(vt[1][E], __builtin_bit_cast(float, T & 0xFFFF0000u));                         \
+  }
+#define SESSD_SS_F_E0(E) SESSD_SS_F_TERM(tq0, E)
+#define SESSD_SS_F_E1(E) SESSD_SS_F_TERM(tq1, E)
+#define SESSD_SS_F_E2(E)                                                                           \
+  {                                                                                                \
+    vdst[(E) * 256] = tq0; vdst[(16 + (E)) * 256] = tq1; vdst[(32 + (E)) * 256] = pk_bf16(vt[0][E], vt[1][E]); \
+  }
+#define SESSD_SS_GAP(F)                                                                            \
+  __builtin_amdgcn_sched_barrier(0);                                                               \
+  F                                                                                                \
+  __builtin_amdgcn_sched_barrier(0);
+  // step KS with the piece F<n> behind its n-th MFMA (SESSD_SS_MMA's order)
+#define SESSD_SS_STEP_T(KS, F0, F1, F2, F3, F4, F5)                                                \
+  {                                                                                                \
+    SESSD_SS_LOADU(((KS) + 3) & 3, kg0 + (KS) + 3)                                                 \
+    __builtin_amdgcn_sched_barrier(0);                                                             \
+    f32x16 a_ = acc[(KS) >> 2][(KS) & 3];                                                          \
+    a_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(us[(KS) & 3][2], bs[0], a_, 0, 0, 0);             \
+    SESSD_SS_GAP(F0)                                                                               \
+    a_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(us[(KS) & 3][1], bs[1], a_, 0, 0, 0);             \
+    SESSD_SS_GAP(F1)                                                                               \
+    a_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(us[(KS) & 3][0], bs[2], a_, 0, 0, 0);             \
+    SESSD_SS_GAP(F2)                                                                               \
+    a_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(us[(KS) & 3][1], bs[0], a_, 0, 0, 0);             \
+    SESSD_SS_GAP(F3)                                                                               \
+    a_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(us[(KS) & 3][0], bs[1], a_, 0, 0, 0);             \
+    SESSD_SS_GAP(F4)                                                                               \
+    a_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(us[(KS) & 3][0], bs[0], a_, 0, 0, 0);             \
+    SESSD_SS_GAP(F5)                                                                               \
+    acc[(KS) >> 2][(KS) & 3] = a_;                                                                 \
+  }
+#define SESSD_SS_ROUND_PIPE()                                                                      \
+  {                                                                                                \
+    const int kg0 = rr * 8;                                                                        \
+    f32x4v ra[2], rb[2];                                                                           \
+    float vt[2][8];                                                                                \
+    unsigned tq0, tq1;                                                                             \
+    unsigned* vdst = reinterpret_cast<unsigned*>(&lds[(voff ^ VBUF_S) + ((8 * h) * 64 + (wave >> 2) * 32 + j) * 4 + (wave & 3)]); \
+    SESSD_SS_LOADP(rr + 1)                                                                         \
+    SESSD_SS_READV(voff, 0)                                                                        \
+    __builtin_amdgcn_sched_barrier(0);                                                             \
+    SESSD_SS_STEP(0)                                                                               \
+    SESSD_SS_STEP(1)                                                                               \
+    SESSD_SS_STEP(2)                                                                               \
+    SESSD_SS_STEP_T(3, SESSD_SS_F_ROWA(0) SESSD_SS_F_ROWA(1), SESSD_SS_F_ROWB(0) SESSD_SS_F_ROWB(1), SESSD_SS_F_MASK(ra, 0),    \
+                    SESSD_SS_F_MASK(ra, 1), SESSD_SS_F_MASK(rb, 0), SESSD_SS_F_MASK(rb, 1))        \
+    SESSD_SS_READV(voff, 1)                                                                        \
+    __builtin_amdgcn_sched_barrier(0);                                                             \
+    SESSD_SS_STEP_T(4, SESSD_SS_F_COLS(0, ra, 0) SESSD_SS_F_COLS(1, ra, 0), SESSD_SS_F_E0(0), SESSD_SS_F_E1(0),              \
+                    SESSD_SS_F_E2(0) SESSD_SS_F_COLS(0, rb, 4), SESSD_SS_F_E0(1) SESSD_SS_F_COLS(1, rb, 4), SESSD_SS_F_E1(1)) \
+    SESSD_SS_STEP_T(5, SESSD_SS_F_E2(1) SESSD_SS_F_E0(2), SESSD_SS_F_E1(2), SESSD_SS_F_E2(2), SESSD_SS_F_E0(3), SESSD_SS_F_E1(3), SESSD_SS_F_E2(3)) \
+    SESSD_SS_STEP_T(6, SESSD_SS_F_E0(4), SESSD_SS_F_E1(4), SESSD_SS_F_E2(4), SESSD_SS_F_E0(5), SESSD_SS_F_E1(5), SESSD_SS_F_E2(5)) \
+    SESSD_SS_STEP_T(7, SESSD_SS_F_E0(6), SESSD_SS_F_E1(6), SESSD_SS_F_E2(6), SESSD_SS_F_E0(7), SESSD_SS_F_E1(7), SESSD_SS_F_E2(7)) \
+    __syncthreads();                                                                               \
+    voff ^= VBUF_S;                                                                                \
+    ++rr;                                                                                          \
+  }
 
     if constexpr (SPLIT) {
       SESSD_SS_LOADP(r0)
@@ -491,8 +603,11 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void conv3x3s1_winograd_sk_kernel(
     }
     int voff = 0;
     int rr = r0;
-    if constexpr (SPLIT) {
+    if constexpr (SPLIT && (VAR & 4)) {
       while (rr < r1) SESSD_SS_ROUND()
+    } else if constexpr (SPLIT) {
+      const float sgn = h ? -1.f : 1.f;
+      while (rr < r1) SESSD_SS_ROUND_PIPE()
     } else {
       while (rr < r1) SESSD_SK_ROUND()
     }
@@ -510,6 +625,17 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void conv3x3s1_winograd_sk_kernel(
 #undef SESSD_SS_MMA
 #undef SESSD_SS_STEP
 #undef SESSD_SS_ROUND
+#undef SESSD_SS_F_MASK
+#undef SESSD_SS_F_ROWA
+#undef SESSD_SS_F_ROWB
+#undef SESSD_SS_F_COLS
+#undef SESSD_SS_F_TERM
+#undef SESSD_SS_F_E0
+#undef SESSD_SS_F_E1
+#undef SESSD_SS_F_E2
+#undef SESSD_SS_GAP
+#undef SESSD_SS_STEP_T
+#undef SESSD_SS_ROUND_PIPE
 
     // ---- epilogue: per 32-cout block, M_xi of all 16 xi through LDS, Y = A^T M A per (cout, tile)
     // The arguments only the epilogue needs are re-read from the kernel-argument segment HERE (through an opaque pointer):
@@ -1051,18 +1177,24 @@ int launch_sk(const float* in, int batch, int nsets, int cin, int h, int w, cons
   if (workgroups > A.total_rounds) workgroups = A.total_rounds >= 8 ? (A.total_rounds & ~7) : A.total_rounds;
   A.counters = (unsigned*)workspace;
   A.scratch = (float*)((char*)workspace + sessd_align((size_t)units * 4, 256));
+  static const int var = [] { const char* e = getenv("SESSD_WINO_VAR"); return e ? atoi(e) & 7 : 0; }();
+  if constexpr (SPLIT) {   // bits 0 and 1 are the f32 loop's
+    if (tile_list) {
+      if (var & 4) SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 4, true, true>), dim3(workgroups), dim3(NW * 64), 0, stream, A);
+      else SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 0, true, true>), dim3(workgroups), dim3(NW * 64), 0, stream, A);
+    } else {
+      if (var & 4) SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 4, false, true>), dim3(workgroups), dim3(NW * 64), 0, stream, A);
+      else SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 0, false, true>), dim3(workgroups), dim3(NW * 64), 0, stream, A);
+    }
+    SESSD_CHECK_LAUNCH();
+    return SESSD_OK;
+  }
   if (tile_list) {   // active-tile mode: the same kernel over a device list of tiles (shares are sized on the device)
-    SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 0, true, SPLIT>), dim3(workgroups), dim3(NW * 64), 0, stream, A);
+    SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 0, true, false>), dim3(workgroups), dim3(NW * 64), 0, stream, A);
     SESSD_CHECK_LAUNCH();
     return SESSD_OK;
   }
-  if constexpr (SPLIT) {
-    SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 0, false, true>), dim3(workgroups), dim3(NW * 64), 0, stream, A);
-    SESSD_CHECK_LAUNCH();
-    return SESSD_OK;
-  }
-  static const int var = [] { const char* e = getenv("SESSD_WINO_VAR"); return e ? atoi(e) & 3 : 0; }();
-  switch (var) {
+  switch (var & 3) {
     case 1: SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 1>), dim3(workgroups), dim3(NW * 64), 0, stream, A); break;
     case 2: SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 2>), dim3(workgroups), dim3(NW * 64), 0, stream, A); break;
     case 3: SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 3>), dim3(workgroups), dim3(NW * 64), 0, stream, A); break;

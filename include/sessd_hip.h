@@ -211,6 +211,30 @@ int sessd_pillar_scatter_bwd(const float* grad_canvas, const int32_t* coors, con
 int sessd_deconv_ks_slice(const float* in, int batch, int cin, int hin, int win, const float* wpk, int s,
                           float* out, int cout, int c_total, int c_off,
                           const float* scale, const float* shift, int relu, sessd_stream_t stream);
+/* The two gradients of that up-sampler without epilogue (csrc/deconv_ks_grad.hip), for the train-mode RPN neck
+ * (sessd_hip.ops.DeconvKsFunction): GEMMs on the exact-f32 matrix cores over the forward's whole argument domain -- s in {1, 2, 4},
+ * cin even and >= 2, cout a positive multiple of 32, ANY hin, win >= 1 -- on contiguous NCHW float32 tensors, no host
+ * synchronisation, no allocation, no floating-point atomics: two calls on the same inputs give the same bits.
+ *   sessd_deconv_ks_dgrad:  grad_in[b][i][y][x] = sum_{o, py, px} grad_out[b][o][s*y + py][s*x + px] * W[i][o][py][px]
+ *     grad_out (batch, cout, s*hin, s*win); grad_in (batch, cin, hin, win), every element written; wpk the weight (cin, cout, s, s)
+ *     re-ordered as floats [py][cout / 2][cout parity][cin][px] (sessd_hip.ops.pack_deconv_ks_dgrad). One launch; an fmaf chain
+ *     over (py, cout, px) in that order.
+ *   sessd_deconv_ks_wgrad:  grad_weight[i][o][py][px] = sum_{b, y, x} in[b][i][y][x] * grad_out[b][o][s*y + py][s*x + px]
+ *     grad_weight in the STORED layout (cin, cout, s, s), every element written. Two launches: the stages of 8 consecutive pixels
+ *     of an image plane (batch * ceil(hin * win / 8) of them) are dealt out in n = min(stages, clamp(2048 / tiles, 8, 128)) equal
+ *     chunks, tiles = ceil(cin / 32 c) * ceil(cout / 32 d) * s with (c, d) = (2, 2), (2, 1), (1, 1) for s = 1, 2, 4; a wave writes
+ *     its chunk's partial into the workspace, a second kernel adds the partials in chunk order.
+ *     sessd_deconv_ks_wgrad_workspace_bytes = n * cin * cout * s * s * 4 (n = 1 for an empty call), 0 outside the domain.
+ * SESSD_EINVAL before any launch: s not in {1, 2, 4}; cin odd or < 2; cout not a positive multiple of 32; batch > 65535; a negative
+ * size; and, for a non-empty call, a NULL tensor (or workspace), a grad_out / wpk not aligned to 4 * s bytes, a workspace not
+ * aligned to 16 bytes or smaller than _workspace_bytes, and a tensor that 32-bit byte offsets cannot address: 2 GiB or more of
+ * one image's grad_out or of the weight (dgrad), of the whole in, the whole grad_out or the weight (wgrad).
+ * batch * hin * win == 0 launches nothing: OK. */
+int sessd_deconv_ks_dgrad(const float* grad_out, int batch, int cin, int hin, int win, const float* wpk, int s, int cout,
+                          float* grad_in, sessd_stream_t stream);
+size_t sessd_deconv_ks_wgrad_workspace_bytes(int batch, int cin, int hin, int win, int cout, int s);
+int sessd_deconv_ks_wgrad(const float* in, const float* grad_out, int batch, int cin, int hin, int win, int cout, int s,
+                          float* grad_weight, void* workspace, size_t workspace_bytes, sessd_stream_t stream);
 
 /* ------------------------------------------------------------------ iou3d_cuda operators (a15)
  * replace det3d/core/iou3d/src/iou3d.cpp:24-115 (boxes_overlap_bev_gpu, boxes_aligned_overlap_bev_gpu,

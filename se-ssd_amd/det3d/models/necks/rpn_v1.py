@@ -177,7 +177,7 @@ class RPN(nn.Module):
     (s = 1, the three-class config: a 1x1 conv with the weight transposed, lowered through the 1x1 kernels); a stride below 1 is a
     strided Conv2d (not in the reference at this commit). Lowered: stride-1/2 3x3 convs, 1x1 convs, the k = 1 stride-1 transposed
     conv, and the k = s transposed up-samplers of stride s >= 2 (s * s output-parity launches of one tap each,
-    ops.pack_deconv2d_ks)."""
+    ops.pack_deconv2d_ks). Train mode (_forward_train): forward and backward of the covered layers on the device, see _train_block."""
 
     def __init__(self, layer_nums, ds_layer_strides, ds_num_filters, us_layer_strides, us_num_filters,
                  num_input_features, norm_cfg=None, name="rpn", logger=None, **kwargs):
@@ -216,9 +216,54 @@ class RPN(nn.Module):
         (logger or logging.getLogger("RPN")).info("Finish RPN Initialization")
         self._low = _Lowered()
 
+    fused_train = True   # train mode on the device: the layers the HIP kernels cover run on them (False: every torch module)
+
+    def _train_block(self, seq, x):
+        """One block / deblock in train mode (batch-statistics BatchNorm, autograd), layer by layer: a conv that
+        ops.conv2d_train_covers (with the ZeroPad2d(1) in front of it, which is its padding) on ops.Conv2dFunction, a transposed conv
+        that ops.deconv_ks_covers on ops.DeconvKsFunction, a plain train-mode BatchNorm2d with the ReLU behind it on
+        ops.bn2d_relu_train; anything else -- a layer the predicates refuse, a stride < 1 "up-sampler" Conv2d, another norm layer,
+        every layer of a CPU tensor or with fused_train = False -- runs its own torch module."""
+        mods = list(seq._modules.values())
+        fused = self.fused_train and x.is_cuda
+        i = 0
+        while i < len(mods):
+            m = mods[i]
+            nxt = mods[i + 1] if i + 1 < len(mods) else None
+            if (fused and isinstance(m, nn.ZeroPad2d) and tuple(m.padding) == (1, 1, 1, 1)
+                    and ops.conv2d_train_covers(nxt, x, padded=True)):
+                x = ops.conv2d_module(x, nxt)
+                i += 2
+            elif fused and ops.conv2d_train_covers(m, x):
+                x = ops.conv2d_module(x, m)
+                i += 1
+            elif fused and ops.deconv_ks_covers(m, x):
+                x = ops.DeconvKsFunction.apply(x, m.weight, int(m.stride[0]))
+                i += 1
+            elif fused and type(m) is nn.BatchNorm2d and m.training and x.dtype == torch.float32:
+                relu = isinstance(nxt, nn.ReLU)
+                x = ops.bn2d_relu_train(x, m, relu)     # SyncBN and its own fallback inside
+                i += 2 if relu else 1
+            else:
+                x = m(x)
+                i += 1
+        return x
+
+    def _forward_train(self, x):
+        """Train mode, composed as rpn_v1.py:107-116; the up-samplers' outputs are joined with torch.cat, whose backward hands
+        every up-sampler its channel slice of the gradient."""
+        ups = []
+        for i in range(len(self.blocks)):
+            x = self._train_block(self.blocks[i], x)
+            if i - self._upsample_start_idx >= 0:
+                ups.append(self._train_block(self.deblocks[i - self._upsample_start_idx], x))
+        return torch.cat(ups, dim=1) if len(ups) > 0 else x
+
     def forward(self, x):
         ups = []
         x = x.float().contiguous()
+        if self.training:
+            return self._forward_train(x)
         for i in range(len(self.blocks)):
             x = _run_block(self._low, "blk%d" % i, self.blocks[i], x)
             if i - self._upsample_start_idx >= 0:

@@ -107,6 +107,9 @@ SIGNATURES = {
     "sessd_pillar_train_bwd_finalize": (i32, [vp, vp, vp, vp, vp, vp, f32, i32, i32, i32, vp, vp, vp, vp]),
     "sessd_pillar_scatter_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     "sessd_deconv_ks_slice":(i32, [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp]),
+    "sessd_deconv_ks_dgrad": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp]),
+    "sessd_deconv_ks_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+    "sessd_deconv_ks_wgrad": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
     "sessd_boxes_pairwise": (i32, [i32, vp, i32, vp, i32, vp, vp]),
     "sessd_boxes_aligned_overlap_bev": (i32, [vp, vp, i32, vp, vp]),
     "sessd_rotate_iou_eval": (i32, [vp, i32, vp, i32, i32, vp, vp]),

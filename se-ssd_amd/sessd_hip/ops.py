@@ -2149,6 +2149,155 @@ def deconv_ks_slice(x, packed, scale, shift, relu, out, c_off):
     return out
 
 
+def _deconv_ks_dims(weight, s, what):
+    """(cin, cout) of a ConvTranspose2d(cin, cout, s, stride=s) weight inside the domain of csrc/deconv_ks*.hip, else ValueError"""
+    s = int(s)
+    if weight.dim() != 4 or s not in (1, 2, 4) or tuple(weight.shape[2:]) != (s, s):
+        raise ValueError("%s: a (cin, cout, s, s) weight with s in {1, 2, 4} expected, got %s, s = %d" % (what, tuple(weight.shape), s))
+    ci, co = int(weight.shape[0]), int(weight.shape[1])
+    if ci < 2 or ci % 2 or co < 32 or co % 32:
+        raise ValueError("%s: even cin and cout %% 32 == 0 expected, got %d -> %d" % (what, ci, co))
+    return ci, co
+
+
+def pack_deconv_ks_dgrad(weight, s):
+    """nn.ConvTranspose2d(Cin, Cout, s, stride=s) weight (Cin, Cout, s, s) for sessd_deconv_ks_dgrad (csrc/deconv_ks_grad.hip), floats:
+        [py][Cout / 2][Cout parity][Cin][px]     out[py][op][h][i][px] = W[i][2 op + h][py][px]
+    One torch permute on the device, a snapshot of the tensor as it is now."""
+    w = weight.detach().to(torch.float32).contiguous()
+    _req(w, torch.float32, "weight")
+    ci, co = _deconv_ks_dims(w, s, "pack_deconv_ks_dgrad")
+    s = int(s)
+    return w.view(ci, co // 2, 2, s, s).permute(3, 1, 2, 0, 4).contiguous()   # [i, op, h, py, px] -> [py, op, h, i, px]
+
+
+def deconv_ks_dgrad(grad_out, weight, s):
+    """Data gradient of ConvTranspose2d(Cin, Cout, s, stride=s): grad_out (B, Cout, s*H, s*W), weight the stored (Cin, Cout, s, s)
+    tensor -> (B, Cin, H, W), one launch (sessd_deconv_ks_dgrad) behind the permute of pack_deconv_ks_dgrad."""
+    _req(grad_out, torch.float32, "grad_out")
+    ci, co = _deconv_ks_dims(weight, s, "deconv_ks_dgrad")
+    s = int(s)
+    if grad_out.dim() != 4 or grad_out.shape[1] != co or grad_out.shape[2] % s or grad_out.shape[3] % s:
+        raise ValueError("deconv_ks_dgrad: grad_out %s does not match the weight %s, s = %d" % (tuple(grad_out.shape), tuple(weight.shape), s))
+    B, H, W = int(grad_out.shape[0]), int(grad_out.shape[2]) // s, int(grad_out.shape[3]) // s
+    wpk = pack_deconv_ks_dgrad(weight, s)
+    gin = torch.empty((B, ci, H, W), dtype=torch.float32, device=grad_out.device)
+    check(lib.sessd_deconv_ks_dgrad(grad_out.data_ptr(), B, ci, H, W, wpk.data_ptr(), s, co, gin.data_ptr(), _stream()), "deconv_ks_dgrad")
+    return gin
+
+
+def deconv_ks_wgrad(x, grad_out, s):
+    """Weight gradient of ConvTranspose2d(Cin, Cout, s, stride=s), in the stored layout (Cin, Cout, s, s): x (B, Cin, H, W), grad_out
+    (B, Cout, s*H, s*W). Two launches (sessd_deconv_ks_wgrad): chunk partials in a cached workspace, then their ordered sum."""
+    _req(x, torch.float32, "x")
+    _req(grad_out, torch.float32, "grad_out")
+    s = int(s)
+    if x.dim() != 4 or grad_out.dim() != 4:
+        raise ValueError("deconv_ks_wgrad: x (B, Cin, H, W) and grad_out (B, Cout, s*H, s*W) expected")
+    B, ci, H, W = (int(v) for v in x.shape)
+    co = int(grad_out.shape[1])
+    if tuple(grad_out.shape) != (B, co, s * H, s * W):
+        raise ValueError("deconv_ks_wgrad: x %s, s = %d does not match grad_out %s" % (tuple(x.shape), s, tuple(grad_out.shape)))
+    gw = torch.empty((ci, co, s, s), dtype=torch.float32, device=x.device)
+    _deconv_ks_dims(gw, s, "deconv_ks_wgrad")
+    if B * H * W == 0:
+        return gw.zero_()
+    ws = workspace(int(lib.sessd_deconv_ks_wgrad_workspace_bytes(B, ci, H, W, co, s)), x.device, "deconv_ks_wgrad")
+    check(lib.sessd_deconv_ks_wgrad(x.data_ptr(), grad_out.data_ptr(), B, ci, H, W, co, s, gw.data_ptr(), ws.data_ptr(), ws.numel(),
+                                    _stream()), "deconv_ks_wgrad")
+    return gw
+
+
+class DeconvKsFunction(torch.autograd.Function):
+    """Differentiable ConvTranspose2d(Cin, Cout, s, stride=s, bias=False), s in {1, 2, 4}, on the HIP kernels: apply(x, weight, s).
+    forward: sessd_deconv_ks_slice into its own (B, Cout, s*H, s*W) tensor (no scale, no shift, no ReLU);
+    backward: sessd_deconv_ks_dgrad and sessd_deconv_ks_wgrad, each only if its gradient is asked for.
+    The forward's packed weight is made by pack_deconv_ks_slice on EVERY call (a permute of at most 2 MB), and so is the data
+    gradient's copy: the re-pack registry has no job for either layout and is left alone here."""
+
+    @staticmethod
+    def forward(ctx, x, weight, s):
+        x = x.float().contiguous()
+        _req(x, torch.float32, "x")
+        s = int(s)
+        packed = pack_deconv_ks_slice(weight, s)
+        if x.dim() != 4 or x.shape[1] != packed.cin:
+            raise ValueError("DeconvKsFunction: x %s does not match the weight %s" % (tuple(x.shape), tuple(weight.shape)))
+        B, _, H, W = x.shape
+        out = torch.empty((B, packed.cout, s * H, s * W), dtype=torch.float32, device=x.device)
+        ctx.save_for_backward(x, weight)
+        ctx.s = s
+        return deconv_ks_slice(x, packed, None, None, False, out, 0)
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, weight = ctx.saved_tensors
+        g = grad.float().contiguous()   # torch.cat's backward hands out a channel slice of the wider map
+        gx = deconv_ks_dgrad(g, weight, ctx.s) if ctx.needs_input_grad[0] else None
+        gw = deconv_ks_wgrad(x, g, ctx.s) if ctx.needs_input_grad[1] else None
+        return gx, gw, None
+
+
+def _device_f32(x):
+    """a float32 (B, C, H, W) tensor on the device"""
+    return torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+
+
+def _device_param(t):
+    """a float32 parameter on the device, or none"""
+    return t is None or (t.is_cuda and t.dtype == torch.float32)
+
+
+def deconv_ks_covers(m, x):
+    """True where DeconvKsFunction runs module m on x: an nn.ConvTranspose2d with kernel = stride in {1, 2, 4} (both axes), no
+    padding / output_padding / dilation / groups / bias, even cin, cout % 32 == 0, and a float32 (B, cin, H, W) device tensor."""
+    if not isinstance(m, torch.nn.ConvTranspose2d) or not _device_f32(x):
+        return False
+    s = m.stride[0]
+    return (tuple(m.kernel_size) == tuple(m.stride) == (s, s) and s in (1, 2, 4) and tuple(m.padding) == (0, 0)
+            and tuple(m.output_padding) == (0, 0) and tuple(m.dilation) == (1, 1) and m.groups == 1 and m.bias is None
+            and m.in_channels >= 2 and m.in_channels % 2 == 0 and m.out_channels >= 32 and m.out_channels % 32 == 0
+            and x.shape[1] == m.in_channels and _device_param(m.weight))
+
+
+def conv2d_train_covers(m, x, padded=False):
+    """True only where ops.conv2d_module(x, m) runs forward AND backward on the HIP kernels (Conv2dFunction has no such check of its
+    own: outside this domain it raises, or asserts, somewhere on the way). m: an nn.Conv2d with k in {1, 3} and stride in {1, 2}
+    (k = 1: stride 1) on both axes, padding k // 2 -- or, with padded=True, the unpadded 3x3 conv behind an nn.ZeroPad2d(1), which is
+    the same layer (x is then the map in FRONT of the pad) -- no dilation, no groups, zero padding mode; x a float32
+    (B, cin, H, W) device tensor. The conditions, each
+    read off the code that would refuse:
+      pack_conv2d (forward and, stride 1, the adjoint layer): cin and cout even;
+      stride 2: even H and W -- the data gradient is the ConvTranspose2d(3, 2, 1, 1) of pack_deconv2d_s2, whose output is twice
+        its input, and sessd_conv2d_wgrad asks for win == 2 * wout;
+      sessd_conv2d_wgrad: wout % 8 == 0, and the whole input and grad_out below 2 GiB (out_fits of sessd_conv2d_mfma asks less).
+    A bias is covered: its gradient (ops.channel_sum) falls back by itself."""
+    if not isinstance(m, torch.nn.Conv2d) or isinstance(m, torch.nn.ConvTranspose2d) or not _device_f32(x):
+        return False
+    k, s = m.kernel_size[0], m.stride[0]
+    if tuple(m.kernel_size) != (k, k) or tuple(m.stride) != (s, s) or k not in (1, 3) or s not in (1, 2) or (k == 1 and s != 1):
+        return False
+    pad = (0, 0) if (padded and k == 3) else (k // 2, k // 2)
+    if padded and k != 3:
+        return False
+    if (m.padding if isinstance(m.padding, str) else tuple(m.padding)) != pad:
+        return False
+    if tuple(m.dilation) != (1, 1) or m.groups != 1 or m.padding_mode != "zeros":
+        return False
+    if not _device_param(m.weight) or not _device_param(m.bias):
+        return False
+    B, ci, H, W = (int(v) for v in x.shape)
+    co = m.out_channels
+    if ci != m.in_channels or ci % 2 or co % 2 or B < 1 or H < 1 or W < 1:
+        return False
+    if s == 2 and (H % 2 or W % 2):
+        return False
+    Ho, Wo = (H + s - 1) // s, (W + s - 1) // s
+    if Wo % 8:
+        return False
+    return B * ci * H * W * 4 < 0x7FFFFFFF and B * co * Ho * Wo * 4 < 0x7FFFFFFF
+
+
 def deconv2d_s2_pair(x, pc_a, pc_b, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a=None, residual_b=None, tile_cfg=4):
     """Two ConvTranspose2d(3, 2, 1, 1) layers of one shape on the SAME input in one launch (sessd_deconv2d_s2_mfma_pair); the same
     bits as two conv2d() calls with that tile_cfg (3, 4, 11 or 12)."""

@@ -2609,11 +2609,12 @@ def conv2d_wgrad(inp, grad_out, ksize, stride, winograd=None):
     B2, co, ho, wo = grad_out.shape
     assert B == B2
     gw = torch.empty((co, ci, ksize, ksize), dtype=torch.float32, device=inp.device)
+    asked = winograd is True   # the caller's own True; the automatic choice below is a bool, too, and must fall through to the direct kernel
     if winograd is None:
         winograd = USE_WINOGRAD and USE_WINOGRAD_WGRAD and hi * wi >= 4096
     if winograd and ksize == 3 and stride == 1:
         need = int(lib.sessd_conv3x3_wgrad_winograd_workspace_bytes(B, ci, co, hi, wi))
-        if not need and winograd is True:
+        if not need and asked:
             raise ValueError("conv2d_wgrad: the Winograd-domain kernel needs cin, cout % 64 == 0, even H, W, W >= 16")
         if need:   # the shape is one the Winograd-domain kernel covers (16 of the 36 products per tile)
             ws = workspace(need, inp.device, "wwgrad")

@@ -621,19 +621,34 @@ int sessd_assign_targets(const float* anchors, int num_anchors, const float* gt_
  *   output pixel = (y*out_mul + out_py, x*out_mul + out_px)
  *   out = act(conv * scale[c] + shift[c]) (+ residual)
  * wpk: packed weights [cin/2][ntaps][2][cout_pad], cout_pad = roundup(cout,32), element
- *   wpk[kp][t][h][co] = W[co][2*kp+h][tap t]. tile_cfg 0..5 selects the wave/workgroup tiling. */
+ *   wpk[kp][t][h][co] = W[co][2*kp+h][tap t].
+ *
+ * Every launch entry below takes the same three argument groups as structs (sessd_hip_types.h), HOST pointers read before the
+ * call returns: `epilogue` (sessd_conv_epilogue_t: scale, shift, relu, residual; NULL = none of them), `list`
+ * (sessd_tile_list_t; NULL = the whole map, else ACTIVE-TILE mode: only the listed 2x2 tiles are computed, see
+ * sessd_bev_tile_activity below) and, for the stream-K kernels, `sk` (sessd_stream_k_t: workspace, workgroups, min_rounds).
+ * A list launch needs an even tile space and the WHOLE batch (not one image) inside 32-bit buffer offsets, and refuses a list
+ * without tiles, count or cap >= 1; anything an entry cannot run returns SESSD_EINVAL before it touches the device.
+ *
+ * tile_cfg, the wave / workgroup tiling of the direct kernel (csrc/dense_conv.hip dispatch_tile has the shapes), per entry:
+ *   sessd_conv2d_mfma             0 - 8, 11, 12, 13 (11 / 12 / 13 = 4 / 3 / 2 with operands fetched two steps ahead); 10 = the
+ *                                 activation-stationary LDS variant (3x3 stride 1, cin % 16 == 0); with a list: 3, 4, 11, 12 and
+ *                                 four effective taps (a 1x1 layer with cin % 8 == 0, or one class of a transposed conv)
+ *   sessd_deconv2d_s2_mfma        0 - 8, 11, 12; 40 / 41 / 42 = both px classes of a row parity in every wave, 4 / 2 / 1 waves per
+ *                                 workgroup (csrc/dense_deconv_pair.hip)
+ *   sessd_deconv2d_s2_mfma_pair   3, 4, 11, 12, with or without a list
+ * The other entries have no tile_cfg (ops.conv2d's numbers 20 - 25 and 30 select among them). */
 int sessd_conv2d_mfma(const float* in, int batch, int cin, int hin, int win, const float* wpk, int ntaps,
                       const int* taps_dy, const int* taps_dx, int in_mul, int tile_h, int tile_w, float* out, int cout,
-                      int hout, int wout, int out_mul, int out_py, int out_px, const float* scale, const float* shift,
-                      int relu, const float* residual, int tile_cfg, sessd_stream_t stream);
+                      int hout, int wout, int out_mul, int out_py, int out_px, const sessd_conv_epilogue_t* epilogue,
+                      const sessd_tile_list_t* list, int tile_cfg, sessd_stream_t stream);
 /* Conv2d(cin, cout, 3, stride 1, padding 1) by fused Winograd F(2x2,3x3) on the f32 matrix cores: 2.25x fewer MFMAs
  * than sessd_conv2d_mfma for the same layer (not bit-identical to it: Winograd rounding, ~1e-6 of the output scale).
  * upk = U = G g G^T packed [cin/2][4][2][cout_pad][4] = [k-step][xi / 4][channel parity][cout][xi % 4], xi = 4*row + col.
  * Even H and W, cin % 8 == 0. variant 0 / 1: operands fetched one / two rounds (8 / 16 input channels) ahead of their
  * use (variant 1: cin % 32 == 0) -- same arithmetic, same results. */
 int sessd_conv3x3_winograd(const float* in, int batch, int cin, int h, int w, const float* upk, float* out, int cout,
-                           const float* scale, const float* shift, int relu, const float* residual, int variant,
-                           sessd_stream_t stream);
+                           const sessd_conv_epilogue_t* epilogue, int variant, sessd_stream_t stream);
 /* Weight packing on the device, one launch each (ops.pack_conv2d / pack_deconv2d_s2 / pack_winograd*; the training step re-packs every
  * dense conv weight for the teacher forward, the student forward and the student data gradient of every iteration).
  * sessd_conv2d_pack_taps: out [cin/2][ntaps][2][cout_pad32], out[kp][t][h][o] = w[o * out_stride + (2 kp + h) * in_stride +
@@ -648,23 +663,21 @@ int sessd_conv3x3_winograd_pack(const float* w, long long out_stride, long long 
                                 float* out, sessd_stream_t stream);
 /* Second generation of the above (csrc/dense_wino_sk.hip): a workgroup handles 32 tiles x ALL couts of a unit (the patch
  * transform runs once per tile block instead of once per 32-cout block) and the rounds of all units are dealt out "stream-K" in
- * equal shares to `workgroups` persistent workgroups (a multiple of 8; 0 = the shape's default), units cut by a share boundary
+ * equal shares to sk->workgroups persistent workgroups (a multiple of 8; 0 = the shape's default), units cut by a share boundary
  * being finished by whichever part arrives last. shape 0: 8 waves x 128 couts per workgroup, one per CU; shape 1: 4 waves x 64
  * couts, two per CU; shape 2: 4 waves x 128 couts (output transform in registers); shape 3: shape 0 on the bf16 matrix cores at
  * f32 accuracy (operands split into three bf16 terms, six products kept; upk = layout 4 of sessd_conv3x3_winograd_pack).
  * upk = U = G g G^T packed [ceil(cout / C)][cin/2][NW][2][32][C/32][16/NW], (NW, C) = (8, 128) / (4, 64);
- * cin % (2 NW) == 0, even H and W. workspace: sessd_conv3x3_winograd_sk_workspace_bytes(...) bytes, zeroed ONCE by the caller
- * (the kernel leaves its counters zero), not shared between launches that may run concurrently. */
+ * cin % (2 NW) == 0, even H and W. sk->workspace: sessd_conv3x3_winograd_sk_workspace_bytes(...) bytes, zeroed ONCE by the caller
+ * (the kernel leaves its counters zero), not shared between launches that may run concurrently.
+ * nsets > 1: several layers of ONE shape in one launch (conv_0 / conv_1 of the SSFA neck, rpn_v1.py:201-210): the batch dimension
+ * is nsets consecutive groups of batch / nsets elements, group s convolved with weight set s (upk = nsets packings back to back,
+ * scale / shift = nsets x cout): one round list, one pipeline fill and one tail instead of nsets.
+ * With a list (nsets 1; shape 0, 1 or 3): see sessd_bev_tile_activity below. */
 size_t sessd_conv3x3_winograd_sk_workspace_bytes(int batch, int h, int w, int cout, int shape, int workgroups);
-int sessd_conv3x3_winograd_sk(const float* in, int batch, int cin, int h, int w, const float* upk, float* out, int cout,
-                              const float* scale, const float* shift, int relu, const float* residual, void* workspace,
-                              size_t workspace_bytes, int shape, int workgroups, sessd_stream_t stream);
-/* Several layers of ONE shape in one launch (conv_0 / conv_1 of the SSFA neck, rpn_v1.py:201-210): the batch dimension is nsets
- * consecutive groups of batch / nsets elements, group s convolved with weight set s (upk = nsets packings back to back, scale /
- * shift = nsets x cout): one round list, one pipeline fill and one tail instead of nsets. nsets == 1 is the call above. */
-int sessd_conv3x3_winograd_sk_sets(const float* in, int batch, int nsets, int cin, int h, int w, const float* upk, float* out,
-                                   int cout, const float* scale, const float* shift, int relu, const float* residual,
-                                   void* workspace, size_t workspace_bytes, int shape, int workgroups, sessd_stream_t stream);
+int sessd_conv3x3_winograd_sk(const float* in, int batch, int nsets, int cin, int h, int w, const float* upk, float* out, int cout,
+                              const sessd_conv_epilogue_t* epilogue, const sessd_tile_list_t* list, const sessd_stream_k_t* sk,
+                              int shape, sessd_stream_t stream);
 /* ACTIVE-TILE mode of the stream-K kernel (csrc/dense_wino_sk.hip, LIST = true; csrc/dense_active.hip). The BEV map entering the
  * neck (`.dense()` of the last sparse level, det3d/models/backbones/scn.py:179-183) is zero outside the sparse backbone's sites, so
  * the first three layers of bottom_up_block_0 (rpn_v1.py:135-148) compute the same per-channel constant in every 2x2-output tile
@@ -682,8 +695,8 @@ int sessd_conv3x3_winograd_sk_sets(const float* in, int batch, int nsets, int ci
  *   sessd_fill_inactive_tiles   out[b][co][tile] = value[co] (the layer's constant, computed by the host from the folded weights;
  *                               one value per output parity class for job.tile = 4 / 6) in the tiles nobody computes, up to 12
  *                               layers per launch
- *   sessd_conv3x3_winograd_sk_active   sessd_conv3x3_winograd_sk (shape 0, 1 or 3) over the listed tiles only (same packed U, same workspace; the
- *                               shares of the round list are sized on the device, workgroups beyond rounds / min_rounds exit;
+ *   sessd_conv3x3_winograd_sk   with a list (shape 0, 1 or 3, nsets 1): the listed tiles only (same packed U, same workspace; the
+ *                               shares of the round list are sized on the device, workgroups beyond rounds / sk->min_rounds exit;
  *                               min_rounds = -k: whole-unit shares of at least k units, no unit cut, no partial sums in memory)
  * Results equal the dense layer's to float32 rounding (tests/test_dense_active_gpu.py); replaces nothing in the reference -- it is
  * how this path avoids arithmetic on constants that ATen's dense conv performs. */
@@ -692,98 +705,74 @@ int sessd_bev_tile_activity(const int32_t* indices, const int32_t* n_dev, int n_
                             int n_steps, uint64_t* tile_mask, int32_t* tile_list, int32_t* n_list, int list_cap, void* workspace,
                             size_t workspace_bytes, sessd_stream_t stream);
 int sessd_fill_inactive_tiles(const sessd_fill_tiles_job_t* jobs, int n_jobs, int batch, sessd_stream_t stream);
-int sessd_conv3x3_winograd_sk_active(const float* in, int batch, int cin, int h, int w, const float* upk, float* out, int cout,
-                                     const float* scale, const float* shift, int relu, const float* residual,
-                                     const int32_t* tile_list, const int32_t* n_list, int list_cap, int min_rounds, void* workspace,
-                                     size_t workspace_bytes, int shape, int workgroups, sessd_stream_t stream);
 /* The convolutions that are NOT 3x3 stride 1 (stride-2 3x3, 1x1, the four output-parity classes of the stride-2 transposed conv;
- * rpn_v1.py:150-210) as an LDS-tiled implicit GEMM, stream-K over `workgroups` persistent workgroups (a multiple of 8, 0 = one
+ * rpn_v1.py:150-210) as an LDS-tiled implicit GEMM, stream-K over sk->workgroups persistent workgroups (a multiple of 8, 0 = one
  * per CU): csrc/dense_conv_sk.hip, tile_cfg 30 of ops.conv2d. nclass (1..4) convolutions that share input, shapes and epilogue
  * but not weights / taps / output phase run as ONE launch. Class c: wpk[c] = device pointer from sessd_conv2d_sk_pack
  * ([ceil(cout/128)][cin/16][ntaps][2048]: the kernel's LDS image, element ((h*2+q)*128 + i)*4 + e of a chunk =
  * w[(cg*128 + i) * out_stride + (cb*16 + 8h + 4q + e) * in_stride + tap_offsets[t]]), ntaps[c] <= 9 taps with input offsets
  * taps_dy / taps_dx[9 c + t] (HOST ints); tile-space pixel (y, x) of tile_h x tile_w reads input (y*in_mul + dy, x*in_mul + dx)
  * and writes output (y*out_mul + out_py[c], x*out_mul + out_px[c]). cin % 16 == 0. Exact float32 arithmetic; the summation
- * order (hence the last bits) is fixed by (shapes, batch, workgroups), not by timing. workspace:
- * sessd_conv2d_sk_workspace_bytes(...) bytes, zeroed ONCE by the caller, not shared between concurrently running launches. */
+ * order (hence the last bits) is fixed by (shapes, batch, workgroups), not by timing. sk->workspace:
+ * sessd_conv2d_sk_workspace_bytes(...) bytes, zeroed ONCE by the caller, not shared between concurrently running launches.
+ * With a list, the ACTIVE-TILE mode of that launch (the stride-2 conv that opens bottom_up_block_1 and the 1x1 trans_0 / trans_1 of
+ * the SSFA neck, rpn_v1.py:150-152,163-172, whose inputs are a per-channel constant away from the sparse sites): only the 2x2
+ * tiles of the TILE SPACE listed in tiles[0 .. min(*count, cap)) (entries image * (tile_h/2 * tile_w/2) + tile:
+ * sessd_bev_tile_activity; a 1x1 layer takes the list of the layer that produced its input) are computed, the other output
+ * pixels are left alone (sessd_fill_inactive_tiles). Shares of the round list are at least sk->min_rounds rounds; same packed
+ * weights and workspace as the whole-map launch. */
 size_t sessd_conv2d_sk_workspace_bytes(int batch, int tile_h, int tile_w, int cout, int nclass, int workgroups);
 int sessd_conv2d_sk_pack(const float* w, long long out_stride, long long in_stride, const int* tap_offsets, int ntaps, int cout,
                          int cin, float* out, sessd_stream_t stream);
 int sessd_conv2d_sk(const float* in, int batch, int cin, int hin, int win, int nclass, const float* const* wpk,
                     const int* ntaps, const int* taps_dy, const int* taps_dx, int in_mul, int tile_h, int tile_w, float* out,
-                    int cout, int hout, int wout, int out_mul, const int* out_py, const int* out_px, const float* scale,
-                    const float* shift, int relu, const float* residual, void* workspace, size_t workspace_bytes, int workgroups,
+                    int cout, int hout, int wout, int out_mul, const int* out_py, const int* out_px,
+                    const sessd_conv_epilogue_t* epilogue, const sessd_tile_list_t* list, const sessd_stream_k_t* sk,
                     sessd_stream_t stream);
-/* ACTIVE-TILE mode of that launch (the stride-2 conv that opens bottom_up_block_1 and the 1x1 trans_0 / trans_1 of the SSFA neck,
- * rpn_v1.py:150-152,163-172, whose inputs are a per-channel constant away from the sparse sites): only the 2x2 tiles of the TILE
- * SPACE listed in tile_list[0 .. min(*n_list, list_cap)) (entries image * (tile_h/2 * tile_w/2) + tile, count on the device:
- * sessd_bev_tile_activity; a 1x1 layer takes the list of the layer that produced its input) are computed, the other output
- * pixels are left alone (sessd_fill_inactive_tiles). Even tile_h, tile_w; the whole batch tensor is addressed through 32-bit
- * offsets. Shares of the round list are at least min_rounds rounds; same packed weights and workspace as sessd_conv2d_sk. */
-int sessd_conv2d_sk_active(const float* in, int batch, int cin, int hin, int win, int nclass, const float* const* wpk,
-                           const int* ntaps, const int* taps_dy, const int* taps_dx, int in_mul, int tile_h, int tile_w, float* out,
-                           int cout, int hout, int wout, int out_mul, const int* out_py, const int* out_px, const float* scale,
-                           const float* shift, int relu, const float* residual, const int32_t* tile_list, const int32_t* n_list,
-                           int list_cap, int min_rounds, void* workspace, size_t workspace_bytes, int workgroups,
-                           sessd_stream_t stream);
 /* ConvTranspose2d(cin, cout, 3, stride 2, padding 1, output_padding 1) as ONE launch over its four output-parity
  * classes (py,px) = (0,0),(0,1),(1,0),(1,1) with 1,2,2,4 taps: wpk4[c] packed like above, taps_dy4/taps_dx4 are
  * 4 rows of 4 ints. input (B,cin,hin,win) -> output (B,cout,2*hin,2*win); cin % 8 == 0. */
 int sessd_deconv2d_s2_mfma(const float* in, int batch, int cin, int hin, int win, const float* const* wpk4,
                            const int* ntaps4, const int* taps_dy4, const int* taps_dx4, float* out, int cout,
-                           const float* scale, const float* shift, int relu, const float* residual, int tile_cfg,
-                           sessd_stream_t stream);
+                           const sessd_conv_epilogue_t* epilogue, int tile_cfg, sessd_stream_t stream);
 /* Two such layers applied to the SAME input (deconv_block_0 / deconv_block_1 of the SSFA neck, rpn_v1.py:224-226) as one launch
- * over their 2 x 4 parity classes; per layer wpk4 / out / scale / shift / residual as above, shared tap tables. tile_cfg 3, 4, 11
- * or 12. The same bits as two single-layer launches. */
+ * over their 2 x 4 parity classes; per layer wpk4 / out / epilogue as above, shared tap tables. The same bits as two single-layer
+ * launches.
+ * ACTIVE-TILE mode of sessd_conv2d_mfma (1x1 layers: trans_0 / trans_1, rpn_v1.py:163-172) and of this pair (rpn_v1.py:175-199,
+ * 224-226) on maps that are a per-channel constant away from the sparse sites (csrc/dense_active.hip): only the 2x2 tiles of the
+ * TILE SPACE listed in tiles[0 .. min(*count, cap)) (entries image * (tile_h/2 * tile_w/2) + tile: sessd_bev_tile_activity) are
+ * computed -- for the transposed convs the tile space is the INPUT map (step 3 of the activity program), a listed tile gives a
+ * 4x4 block of both outputs --, the other output pixels are left alone (sessd_fill_inactive_tiles, tile = 4 with one constant per
+ * output parity class for the transposed convs). The launch is sized for the whole map, workgroups beyond the device count leave
+ * at once. Per computed pixel the code of the whole-map launch: the same bits. */
 int sessd_deconv2d_s2_mfma_pair(const float* in, int batch, int cin, int hin, int win, const float* const* wpk4_a,
                                 const float* const* wpk4_b, const int* ntaps4, const int* taps_dy4, const int* taps_dx4,
-                                float* out_a, float* out_b, int cout, const float* scale_a, const float* shift_a,
-                                const float* scale_b, const float* shift_b, int relu, const float* residual_a,
-                                const float* residual_b, int tile_cfg, sessd_stream_t stream);
-/* ACTIVE-TILE mode of sessd_conv2d_mfma (1x1 layers: trans_0 / trans_1, rpn_v1.py:163-172) and of sessd_deconv2d_s2_mfma_pair
- * (rpn_v1.py:175-199, 224-226) on maps that are a per-channel constant away from the sparse sites (csrc/dense_active.hip): only the
- * 2x2 tiles of the TILE SPACE listed in tile_list[0 .. min(*n_list, list_cap)) (entries image * (tile_h/2 * tile_w/2) + tile, count
- * on the device: sessd_bev_tile_activity) are computed -- for the transposed convs the tile space is the INPUT map (step 3 of the
- * activity program), a listed tile gives a 4x4 block of both outputs --, the other output pixels are left alone
- * (sessd_fill_inactive_tiles, tile = 4 with one constant per output parity class for the transposed convs). The launch is sized
- * for the whole map, workgroups beyond the device count leave at once. Four effective taps (a 1x1 layer with cin % 8 == 0 or a
- * class of the transposed conv), tile_cfg 3 / 4 / 11 / 12, even tile_h / tile_w, the whole batch inside 32-bit buffer offsets.
- * Per computed pixel the code of the plain launch: the same bits. */
-int sessd_conv2d_mfma_active(const float* in, int batch, int cin, int hin, int win, const float* wpk, int ntaps, const int* taps_dy,
-                             const int* taps_dx, int in_mul, int tile_h, int tile_w, float* out, int cout, int hout, int wout,
-                             int out_mul, int out_py, int out_px, const float* scale, const float* shift, int relu,
-                             const float* residual, const int32_t* tile_list, const int32_t* n_list, int list_cap, int tile_cfg,
-                             sessd_stream_t stream);
-int sessd_deconv2d_s2_mfma_pair_active(const float* in, int batch, int cin, int hin, int win, const float* const* wpk4_a,
-                                       const float* const* wpk4_b, const int* ntaps4, const int* taps_dy4, const int* taps_dx4,
-                                       float* out_a, float* out_b, int cout, const float* scale_a, const float* shift_a,
-                                       const float* scale_b, const float* shift_b, int relu, const float* residual_a,
-                                       const float* residual_b, const int32_t* tile_list, const int32_t* n_list, int list_cap,
-                                       int tile_cfg, sessd_stream_t stream);
-/* sessd_deconv2d_s2_mfma_pair_active on the bf16 matrix cores at f32 accuracy (csrc/dense_deconv_split.hip): every operand split
+                                float* out_a, float* out_b, int cout, const sessd_conv_epilogue_t* epilogue_a,
+                                const sessd_conv_epilogue_t* epilogue_b, const sessd_tile_list_t* list, int tile_cfg,
+                                sessd_stream_t stream);
+/* The list launch of sessd_deconv2d_s2_mfma_pair on the bf16 matrix cores at f32 accuracy (csrc/dense_deconv_split.hip): every operand split
  * into three bf16 terms, six products per operand pair, f32 accumulation; the same contract (listed 2x2 input tiles -> 4x4 blocks
  * of both outputs, nothing else touched). wsplit_a / wsplit_b: each layer's (cin, cout, 3, 3) weight as three bf16 planes in the
  * kernel's fragment order, [ceil(cout / 128)][cin / 16][tap 9][plane 3][cout block 4][lane 64][8] (ops.pack_deconv2d_s2(w).wsplit());
  * the tap tables are the fixed ones of a stride-2 3x3 transposed conv. cin % 16 == 0, even hin / win, the whole batch inside
- * 32-bit buffer offsets; anything else returns SESSD_EINVAL. One workgroup per (16 list entries, 128 couts, layer), sized from
- * list_cap; a listed block's bits do not depend on the rest of the list. */
+ * 32-bit buffer offsets, one activation for both layers (epilogue_a->relu and epilogue_b->relu both set or both clear); anything
+ * else returns SESSD_EINVAL. One workgroup per (16 list entries, 128 couts, layer), sized from list->cap; a listed block's bits do
+ * not depend on the rest of the list. */
 int sessd_deconv2d_s2_pair_split_active(const float* in, int batch, int cin, int hin, int win, const void* wsplit_a,
-                                        const void* wsplit_b, float* out_a, float* out_b, int cout, const float* scale_a,
-                                        const float* shift_a, const float* scale_b, const float* shift_b, int relu,
-                                        const float* residual_a, const float* residual_b, const int32_t* tile_list,
-                                        const int32_t* n_list, int list_cap, sessd_stream_t stream);
+                                        const void* wsplit_b, float* out_a, float* out_b, int cout,
+                                        const sessd_conv_epilogue_t* epilogue_a, const sessd_conv_epilogue_t* epilogue_b,
+                                        const sessd_tile_list_t* list, sessd_stream_t stream);
 /* Conv2d(cin, cout, 3, stride 2, padding 1) + scale / shift / ReLU (+ residual) over a tile list on the bf16 matrix cores at f32
- * accuracy (csrc/dense_conv_s2_split.hip): the contract of sessd_conv2d_sk_active for that layer -- the four output pixels of
- * every listed 2x2 tile of the OUTPUT map (entries image * (hout/2 * wout/2) + tile, count on the device, at most list_cap), all
+ * accuracy (csrc/dense_conv_s2_split.hip): the contract of sessd_conv2d_sk's list launch for that layer -- the four output pixels of
+ * every listed 2x2 tile of the OUTPUT map (entries image * (hout/2 * wout/2) + tile, count on the device, at most list->cap), all
  * couts; nothing else touched, entries outside the maps ignored, no workspace. wsplit: the (cout, cin, 3, 3) weight as three bf16
  * planes in the kernel's fragment order, [ceil(cout / 128)][cin / 16][tap 9 = 3 ky + kx][plane 3][cout block 4][lane 64][8]
  * (ops.pack_conv2d_s2_split). cin % 16 == 0, even hout / wout, hin in {2 hout - 1, 2 hout} and win likewise, the whole batch
  * inside 32-bit buffer offsets; anything else returns SESSD_EINVAL. One workgroup per (16 list entries, 128 couts), sized from
- * list_cap; a listed tile's bits do not depend on the rest of the list. */
+ * list->cap; a listed tile's bits do not depend on the rest of the list. */
 int sessd_conv2d_s2_split_active(const float* in, int batch, int cin, int hin, int win, const void* wsplit, float* out, int cout,
-                                 int hout, int wout, const float* scale, const float* shift, int relu, const float* residual,
-                                 const int32_t* tile_list, const int32_t* n_list, int list_cap, sessd_stream_t stream);
+                                 int hout, int wout, const sessd_conv_epilogue_t* epilogue, const sessd_tile_list_t* list,
+                                 sessd_stream_t stream);
 /* rpn_v1.py:227-233: softmax over the two 1-channel weight maps and the weighted sum of x0, x1 */
 int sessd_ssfa_fuse(const float* x0, const float* x1, const float* w0, const float* w1, float bn_scale0,
                     float bn_shift0, float bn_scale1, float bn_shift1, int batch, int channels, int num_pixels,

@@ -2,6 +2,7 @@
 #ifndef SESSD_HIP_TYPES_H
 #define SESSD_HIP_TYPES_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 /* One strided SparseConv3d step of a chain of sparse levels: level l-1 -> level l (level 0 = the voxels). */
@@ -42,6 +43,33 @@ typedef struct {
   int32_t kind, flip, layout;
   int32_t block_start, pad_;
 } sessd_dense_pack_job_t;
+
+/* The three argument groups every dense launch entry shares (sessd_hip.h, "dense BEV neck"). An entry takes them as HOST
+ * pointers and reads them before it returns; the pointers inside are DEVICE pointers. */
+typedef struct {
+  const float* scale;     /* device [cout] or NULL (1): the folded BatchNorm, out = act(conv * scale + shift) + residual */
+  const float* shift;     /* device [cout] or NULL (0) */
+  const float* residual;  /* device, the shape of the output, or NULL: added after the activation */
+  int32_t relu;           /* != 0: act = max(., 0) */
+} sessd_conv_epilogue_t;
+
+/* The 2x2 tiles a list launch computes (sessd_bev_tile_activity builds both arrays): tiles[0 .. min(*count, cap)), entries
+ * image * tiles per image + tile. A NULL sessd_tile_list_t* means the whole map; one without tiles, count or with cap < 1 is
+ * refused. */
+typedef struct {
+  const int32_t* tiles;   /* device [cap] */
+  const int32_t* count;   /* device, one int */
+  int32_t cap;
+} sessd_tile_list_t;
+
+/* The stream-K block of sessd_conv3x3_winograd_sk / sessd_conv2d_sk. */
+typedef struct {
+  void* workspace;        /* device, the entry's *_workspace_bytes(), zeroed ONCE by the caller */
+  size_t workspace_bytes;
+  int32_t workgroups;     /* persistent workgroups: a multiple of 8, 0 = the kernel's default */
+  int32_t min_rounds;     /* read only with a tile list: a share of the round list holds at least this many rounds (< 1: 1);
+                             sessd_conv3x3_winograd_sk also takes -k: whole-unit shares of at least k units */
+} sessd_stream_k_t;
 
 /* One layer of sessd_fill_inactive_tiles: out (batch, cout, h, w), value[cout], tile_mask[batch][mask_th][2] 64-bit words (bit tx of
  * a row's 128 bits set = computed tile; mask_th >= h/2 rows per image), as sessd_bev_tile_activity writes them. */

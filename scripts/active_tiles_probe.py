@@ -1,5 +1,5 @@
 """Times the first three SSFA layers (3x3 128->128 @200x176) dense (tile_cfg 22 / 23) against the active-tile mode
-(sessd_bev_tile_activity + sessd_fill_inactive_tiles + sessd_conv3x3_winograd_sk_active) on the BEV occupancy of synthetic
+(sessd_bev_tile_activity + sessd_fill_inactive_tiles + sessd_conv3x3_winograd_sk over a tile list) on the BEV occupancy of synthetic
 20 k-point scans (the site pixels come from a CPU restatement of the strided site rule; random features and weights -- only the
 geometry matters for the time). Prints one JSON line."""
 import json

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sessd_hip_types.h"
+
 #define SESSD_WAVE 64
 
 // Every C-ABI entry point returns 0 on success or a hipError_t / negative
@@ -64,6 +66,20 @@ int sessd_voxelize_front(const float* points, int batch, int points_per_frame, i
 
 static inline __host__ __device__ int sessd_divup(int a, int b) { return (a + b - 1) / b; }
 static inline __host__ __device__ size_t sessd_align(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// The dense launch entries' shared argument groups (sessd_hip_types.h) into a kernel's argument struct, whichever it is: the
+// epilogue (NULL: none) into A.scale / shift / residual / relu, the tile list (NULL: the whole map) into A.tile_list / n_list /
+// list_cap. An entry refuses (SESSD_EINVAL) a list that is not sessd_tile_list_ok: no tiles, no count or no room.
+template <class Args>
+inline void sessd_take_epilogue(Args& A, const sessd_conv_epilogue_t* e) {
+  A.scale = e ? e->scale : nullptr; A.shift = e ? e->shift : nullptr; A.residual = e ? e->residual : nullptr;
+  A.relu = e ? e->relu : 0;
+}
+template <class Args>
+inline void sessd_take_tile_list(Args& A, const sessd_tile_list_t* l) {
+  A.tile_list = l ? l->tiles : nullptr; A.n_list = l ? l->count : nullptr; A.list_cap = l ? l->cap : 0;
+}
+inline bool sessd_tile_list_ok(const sessd_tile_list_t* l) { return l->tiles && l->count && l->cap >= 1; }
 
 // ---- open-addressing hash: linear cell key -> row ------------------------
 // EMPTY key is 0x7F7F7F7F so that one hipMemsetAsync(0x7F) clears keys,

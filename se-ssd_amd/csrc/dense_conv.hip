@@ -856,14 +856,16 @@ inline bool out_fits(int cout, int hout, int wout) { return (long long)cout * ho
 
 int fill_args(ConvArgs& A, const float* in, int cin, int hin, int win, const float* wpk, int ntaps, const int* dy,
               const int* dx, int in_mul, int tile_h, int tile_w, float* out, int cout, int hout, int wout, int out_mul,
-              int py, int px, const float* scale, const float* shift, int relu, const float* residual) {
-  A.in = in; A.wpk = wpk; A.out = out; A.scale = scale; A.shift = shift; A.residual = residual;
+              int py, int px, const sessd_conv_epilogue_t* epilogue, const sessd_tile_list_t* list = nullptr, int batch = 1) {
+  A.in = in; A.wpk = wpk; A.out = out;
+  sessd_take_epilogue(A, epilogue);
   A.cin = cin; A.hin = hin; A.win = win;
   A.cout = cout; A.cout_pad = sessd_divup(cout, 32) * 32; A.hout = hout; A.wout = wout;
   A.ht = tile_h; A.wt = tile_w;
   A.in_mul = in_mul; A.out_mul = out_mul; A.out_py = py; A.out_px = px;
-  A.relu = relu;
-  A.tile_list = nullptr; A.n_list = nullptr; A.list_cap = 0; A.ntiles2 = 1; A.tw2 = 1; A.lbatch = 1;
+  // a list launch (list_fits checked it): the 2x2-tile grid of the tile space, and the images the buffers hold
+  sessd_take_tile_list(A, list);
+  A.ntiles2 = list ? (tile_h / 2) * (tile_w / 2) : 1; A.tw2 = list ? tile_w / 2 : 1; A.lbatch = list ? batch : 1;
   int group = 1;
   const int pairs = cin / 2;
   if (ntaps == 1 && pairs % 4 == 0) group = 4;
@@ -878,20 +880,43 @@ int fill_args(ConvArgs& A, const float* in, int cin, int hin, int win, const flo
   return eff;
 }
 
+// What a list launch needs beyond the whole-map launch: tiles, their count and room, an even tile space to cut into 2x2 tiles, and
+// the WHOLE batch inside 32-bit buffer offsets (the image is part of the lane offsets).
+bool list_fits(const sessd_tile_list_t* list, int tile_h, int tile_w, int batch, int cin, int hin, int win, int cout, int hout, int wout) {
+  return sessd_tile_list_ok(list) && !(tile_h & 1) && !(tile_w & 1) &&
+         (long long)batch * cout * hout * wout * 4 < 0x7fffffffLL && (long long)batch * cin * hin * win * 4 < 0x7fffffffLL;
+}
+
 }  // namespace
 
 extern "C" {
 
 // Generic conv launcher. taps_dy/taps_dx: host int[ntaps] input offsets; wpk packed [cin/2][ntaps][2][cout_pad]
-// (cout_pad = cout rounded up to 32, padding columns zero). tile_cfg selects the wave/workgroup tiling (0..5).
+// (cout_pad = cout rounded up to 32, padding columns zero). tile_cfg selects the wave/workgroup tiling (dispatch_tile), 10 the LDS
+// variant. list != NULL, ACTIVE-TILE mode (csrc/dense_active.hip; rpn_v1.py:163-172 on maps that are a per-channel constant away
+// from the sparse sites): only the 2x2 tiles of the TILE SPACE listed in tiles[0 .. min(*count, cap)) (entries image *
+// (tile_h/2 * tile_w/2) + tile) are computed, the other output pixels are left alone. The launch is sized for the whole map;
+// workgroups beyond the count leave at once. Four effective taps, tile_cfg 3 / 4 / 11 / 12. Per computed pixel the code of the
+// whole-map launch: the same bits.
 int sessd_conv2d_mfma(const float* in, int batch, int cin, int hin, int win, const float* wpk, int ntaps,
                       const int* taps_dy, const int* taps_dx, int in_mul, int tile_h, int tile_w, float* out, int cout,
-                      int hout, int wout, int out_mul, int out_py, int out_px, const float* scale, const float* shift,
-                      int relu, const float* residual, int tile_cfg, hipStream_t stream) {
-  if (cin % 2 || ntaps < 1 || ntaps > 9 || batch < 1 || cout < 1 || !out_fits(cout, hout, wout)) return SESSD_EINVAL;
+                      int hout, int wout, int out_mul, int out_py, int out_px, const sessd_conv_epilogue_t* epilogue,
+                      const sessd_tile_list_t* list, int tile_cfg, hipStream_t stream) {
+  if (cin % 2 || ntaps < 1 || ntaps > 9 || batch < 1 || cout < 1) return SESSD_EINVAL;
+  if (list ? !list_fits(list, tile_h, tile_w, batch, cin, hin, win, cout, hout, wout) : !out_fits(cout, hout, wout)) return SESSD_EINVAL;
   ConvArgs A;
   const int eff = fill_args(A, in, cin, hin, win, wpk, ntaps, taps_dy, taps_dx, in_mul, tile_h, tile_w, out, cout, hout,
-                            wout, out_mul, out_py, out_px, scale, shift, relu, residual);
+                            wout, out_mul, out_py, out_px, epilogue, list, batch);
+  if (list) {
+    if (eff != 4) return SESSD_EINVAL;   // 1x1 layers with cin % 8 == 0 (four cin pairs per k-step) and 4-tap classes
+    switch (tile_cfg) {
+      case 3: return launch_conv_list<1, 1, 4, 1, false>(A, batch, stream);
+      case 4: return launch_conv_list<1, 1, 1, 4, false>(A, batch, stream);
+      case 11: return launch_conv_list<1, 1, 1, 4, true>(A, batch, stream);
+      case 12: return launch_conv_list<1, 1, 4, 1, true>(A, batch, stream);
+      default: return SESSD_EINVAL;
+    }
+  }
   if (tile_cfg == 10) {  // activation-stationary LDS variant (3x3, stride 1, cin % 16 == 0)
     if (eff != 9 || in_mul != 1 || out_mul != 1 || cin % 16 || hin != tile_h || win != tile_w) return SESSD_EINVAL;
     dim3 grid(sessd_divup(tile_h * tile_w, 32), sessd_divup(A.cout_pad, 128), batch);
@@ -912,13 +937,12 @@ int sessd_conv2d_mfma(const float* in, int batch, int cin, int hin, int win, con
 // [cin/2][4][2][cout_pad][4] (xi = 4*row + col of the 4x4 transform domain, row-major outer/inner). Even H, W;
 // cin % 8 == 0. variant 0 / 1 = loads one / two rounds ahead of their use.
 int sessd_conv3x3_winograd(const float* in, int batch, int cin, int h, int w, const float* upk, float* out, int cout,
-                           const float* scale, const float* shift, int relu, const float* residual, int variant,
-                           hipStream_t stream) {
+                           const sessd_conv_epilogue_t* epilogue, int variant, hipStream_t stream) {
   if (cin % 8 || (h & 1) || (w & 1) || batch < 1 || cout < 1) return SESSD_EINVAL;
   if (variant < 0 || variant > 1 || (variant == 1 && cin % 32)) return SESSD_EINVAL;
   ConvArgs A;
   const int z9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  fill_args(A, in, cin, h, w, upk, 9, z9, z9, 1, h, w, out, cout, h, w, 1, 0, 0, scale, shift, relu, residual);
+  fill_args(A, in, cin, h, w, upk, 9, z9, z9, 1, h, w, out, cout, h, w, 1, 0, 0, epilogue);
   const int ntiles = (h / 2) * (w / 2);
   dim3 grid(sessd_divup(ntiles, 32) * sessd_divup(A.cout_pad, 32), 1, batch);
   if (variant == 1)
@@ -1100,8 +1124,7 @@ int sessd_conv3x3_winograd_pack(const float* w, long long out_stride, long long 
 // tile_cfg 40 .. 42: both px classes of a row parity in every wave, whole-line stores (dense_deconv_pair.hip)
 }  // extern "C"
 int sessd_deconv_pair_launch(const float* in, int batch, int cin, int hin, int win, const float* const* wpk4, float* out, int cout,
-                             const float* scale, const float* shift, int relu, const float* residual, int variant,
-                             hipStream_t stream);
+                             const sessd_conv_epilogue_t* epilogue, int variant, hipStream_t stream);
 extern "C" {
 
 // ConvTranspose2d(cin, cout, 3, stride 2, padding 1, output_padding 1) as ONE launch over its four output-parity
@@ -1109,8 +1132,7 @@ extern "C" {
 // (0,0),(0,1),(1,0),(1,1) with 1,2,2,4 taps; input (B,cin,hin,win) -> output (B,cout,2*hin,2*win).
 int sessd_deconv2d_s2_mfma(const float* in, int batch, int cin, int hin, int win, const float* const* wpk4,
                            const int* ntaps4, const int* taps_dy4, const int* taps_dx4, float* out, int cout,
-                           const float* scale, const float* shift, int relu, const float* residual, int tile_cfg,
-                           hipStream_t stream) {
+                           const sessd_conv_epilogue_t* epilogue, int tile_cfg, hipStream_t stream) {
   if (cin % 8 || batch < 1 || cout < 1 || !out_fits(cout, 2 * hin, 2 * win)) return SESSD_EINVAL;
   if (tile_cfg >= 40 && tile_cfg <= 42) {
     // the paired kernel hard-codes the class tap tables of ops.pack_deconv2d_s2: refuse anything else
@@ -1122,90 +1144,37 @@ int sessd_deconv2d_s2_mfma(const float* in, int batch, int cin, int hin, int win
       for (int t = 0; t < nt[c]; ++t)
         if (taps_dy4[4 * c + t] != dy[4 * c + t] || taps_dx4[4 * c + t] != dx[4 * c + t]) return SESSD_EINVAL;
     }
-    return sessd_deconv_pair_launch(in, batch, cin, hin, win, wpk4, out, cout, scale, shift, relu, residual, tile_cfg - 40, stream);
+    return sessd_deconv_pair_launch(in, batch, cin, hin, win, wpk4, out, cout, epilogue, tile_cfg - 40, stream);
   }
   ConvArgs A[4];
   for (int c = 0; c < 4; ++c) {
     const int eff = fill_args(A[c], in, cin, hin, win, wpk4[c], ntaps4[c], taps_dy4 + 4 * c, taps_dx4 + 4 * c, 1, hin, win,
-                              out, cout, 2 * hin, 2 * win, 2, c >> 1, c & 1, scale, shift, relu, residual);
+                              out, cout, 2 * hin, 2 * win, 2, c >> 1, c & 1, epilogue);
     if (eff != 4) return SESSD_EINVAL;
   }
   return dispatch_tile<4>(A, 4, batch, tile_cfg, stream);
 }
 
 // Two ConvTranspose2d(cin, cout, 3, 2, 1, 1) layers applied to the SAME input (deconv_block_0 / deconv_block_1 of the SSFA neck)
-// as one launch over their 2 x 4 parity classes: per layer wpk4 / out / scale / shift / residual as in sessd_deconv2d_s2_mfma,
-// shared tap tables. tile_cfg 3, 4, 11 or 12. Per class the code of the single-layer launch: the same bits.
+// as one launch over their 2 x 4 parity classes: per layer wpk4 / out / epilogue as in sessd_deconv2d_s2_mfma, shared tap tables.
+// tile_cfg 3, 4, 11 or 12. Per class the code of the single-layer launch: the same bits.
+// list != NULL, ACTIVE-TILE mode (csrc/dense_active.hip; rpn_v1.py:175-199): the tile space is the INPUT map, a listed 2x2 tile
+// (entries image * (hin/2 * win/2) + tile) gives a 4x4 block of both outputs, the other output pixels are left alone. The launch is
+// sized for the whole map; workgroups beyond the count leave at once.
 int sessd_deconv2d_s2_mfma_pair(const float* in, int batch, int cin, int hin, int win, const float* const* wpk4_a,
                                 const float* const* wpk4_b, const int* ntaps4, const int* taps_dy4, const int* taps_dx4,
-                                float* out_a, float* out_b, int cout, const float* scale_a, const float* shift_a,
-                                const float* scale_b, const float* shift_b, int relu, const float* residual_a,
-                                const float* residual_b, int tile_cfg, hipStream_t stream) {
-  if (cin % 8 || batch < 1 || cout < 1 || !out_fits(cout, 2 * hin, 2 * win)) return SESSD_EINVAL;
+                                float* out_a, float* out_b, int cout, const sessd_conv_epilogue_t* epilogue_a,
+                                const sessd_conv_epilogue_t* epilogue_b, const sessd_tile_list_t* list, int tile_cfg,
+                                hipStream_t stream) {
+  if (cin % 8 || batch < 1 || cout < 1) return SESSD_EINVAL;
+  if (list ? !list_fits(list, hin, win, batch, cin, hin, win, cout, 2 * hin, 2 * win) : !out_fits(cout, 2 * hin, 2 * win)) return SESSD_EINVAL;
   ConvArgs A[8];
   for (int c = 0; c < 4; ++c)
     for (int l = 0; l < 2; ++l) {
       const int eff = fill_args(A[2 * c + l], in, cin, hin, win, (l ? wpk4_b : wpk4_a)[c], ntaps4[c], taps_dy4 + 4 * c, taps_dx4 + 4 * c,
-                                1, hin, win, l ? out_b : out_a, cout, 2 * hin, 2 * win, 2, c >> 1, c & 1, l ? scale_b : scale_a,
-                                l ? shift_b : shift_a, relu, l ? residual_b : residual_a);
+                                1, hin, win, l ? out_b : out_a, cout, 2 * hin, 2 * win, 2, c >> 1, c & 1, l ? epilogue_b : epilogue_a,
+                                list, batch);
       if (eff != 4) return SESSD_EINVAL;
-    }
-  switch (tile_cfg) {
-    case 3: return launch_conv8<1, 1, 4, 1, false>(A, batch, stream);
-    case 4: return launch_conv8<1, 1, 1, 4, false>(A, batch, stream);
-    case 11: return launch_conv8<1, 1, 1, 4, true>(A, batch, stream);
-    case 12: return launch_conv8<1, 1, 4, 1, true>(A, batch, stream);
-    default: return SESSD_EINVAL;
-  }
-}
-
-// ACTIVE-TILE mode of the two launches above (csrc/dense_active.hip; rpn_v1.py:163-199 on maps that are a per-channel constant
-// away from the sparse sites): only the 2x2 tiles of the TILE SPACE listed in tile_list[0 .. min(*n_list, list_cap)) (entries
-// image * (tile_h/2 * tile_w/2) + tile; count on the device) are computed -- for the transposed convs the tile space is the INPUT
-// map, a listed tile gives a 4x4 block of output pixels --, the other output pixels are left alone. The launch is sized for the
-// whole map; workgroups beyond the count leave at once. Even tile_h / tile_w, the whole batch inside 32-bit buffer offsets.
-// Per computed pixel the code of the plain launch: the same bits.
-int sessd_conv2d_mfma_active(const float* in, int batch, int cin, int hin, int win, const float* wpk, int ntaps, const int* taps_dy,
-                             const int* taps_dx, int in_mul, int tile_h, int tile_w, float* out, int cout, int hout, int wout,
-                             int out_mul, int out_py, int out_px, const float* scale, const float* shift, int relu,
-                             const float* residual, const int32_t* tile_list, const int32_t* n_list, int list_cap, int tile_cfg,
-                             hipStream_t stream) {
-  if (cin % 2 || ntaps < 1 || ntaps > 9 || batch < 1 || cout < 1 || !tile_list || !n_list || list_cap < 1 || (tile_h & 1) || (tile_w & 1))
-    return SESSD_EINVAL;
-  if ((long long)batch * cout * hout * wout * 4 >= 0x7fffffffLL || (long long)batch * cin * hin * win * 4 >= 0x7fffffffLL) return SESSD_EINVAL;
-  ConvArgs A;
-  const int eff = fill_args(A, in, cin, hin, win, wpk, ntaps, taps_dy, taps_dx, in_mul, tile_h, tile_w, out, cout, hout, wout, out_mul,
-                            out_py, out_px, scale, shift, relu, residual);
-  if (eff != 4) return SESSD_EINVAL;   // 1x1 layers with cin % 8 == 0 (four cin pairs per k-step) and 4-tap classes
-  A.tile_list = tile_list; A.n_list = n_list; A.list_cap = list_cap; A.ntiles2 = (tile_h / 2) * (tile_w / 2); A.tw2 = tile_w / 2;
-  A.lbatch = batch;
-  switch (tile_cfg) {
-    case 3: return launch_conv_list<1, 1, 4, 1, false>(A, batch, stream);
-    case 4: return launch_conv_list<1, 1, 1, 4, false>(A, batch, stream);
-    case 11: return launch_conv_list<1, 1, 1, 4, true>(A, batch, stream);
-    case 12: return launch_conv_list<1, 1, 4, 1, true>(A, batch, stream);
-    default: return SESSD_EINVAL;
-  }
-}
-
-int sessd_deconv2d_s2_mfma_pair_active(const float* in, int batch, int cin, int hin, int win, const float* const* wpk4_a,
-                                       const float* const* wpk4_b, const int* ntaps4, const int* taps_dy4, const int* taps_dx4,
-                                       float* out_a, float* out_b, int cout, const float* scale_a, const float* shift_a,
-                                       const float* scale_b, const float* shift_b, int relu, const float* residual_a,
-                                       const float* residual_b, const int32_t* tile_list, const int32_t* n_list, int list_cap,
-                                       int tile_cfg, hipStream_t stream) {
-  if (cin % 8 || batch < 1 || cout < 1 || !tile_list || !n_list || list_cap < 1 || (hin & 1) || (win & 1)) return SESSD_EINVAL;
-  if ((long long)batch * cout * 4 * hin * win * 4 >= 0x7fffffffLL || (long long)batch * cin * hin * win * 4 >= 0x7fffffffLL) return SESSD_EINVAL;
-  ConvArgs A[8];
-  for (int c = 0; c < 4; ++c)
-    for (int l = 0; l < 2; ++l) {
-      ConvArgs& C = A[2 * c + l];
-      const int eff = fill_args(C, in, cin, hin, win, (l ? wpk4_b : wpk4_a)[c], ntaps4[c], taps_dy4 + 4 * c, taps_dx4 + 4 * c, 1, hin, win,
-                                l ? out_b : out_a, cout, 2 * hin, 2 * win, 2, c >> 1, c & 1, l ? scale_b : scale_a,
-                                l ? shift_b : shift_a, relu, l ? residual_b : residual_a);
-      if (eff != 4) return SESSD_EINVAL;
-      C.tile_list = tile_list; C.n_list = n_list; C.list_cap = list_cap; C.ntiles2 = (hin / 2) * (win / 2); C.tw2 = win / 2;
-      C.lbatch = batch;
     }
   switch (tile_cfg) {
     case 3: return launch_conv8<1, 1, 4, 1, false>(A, batch, stream);

@@ -319,19 +319,20 @@ extern "C" {
 // ceil(cout / 128) * cin / 16 * 27 * 4096 bytes). cin % 16 == 0, even hout / wout, hin in {2 hout - 1, 2 hout} and win likewise,
 // the whole batch inside 32-bit offsets. One workgroup of 4 waves per (16 list entries, 128 couts), two per CU; no scratch.
 int sessd_conv2d_s2_split_active(const float* in, int batch, int cin, int hin, int win, const void* wsplit, float* out, int cout,
-                                 int hout, int wout, const float* scale, const float* shift, int relu, const float* residual,
-                                 const int32_t* tile_list, const int32_t* n_list, int list_cap, hipStream_t stream) {
+                                 int hout, int wout, const sessd_conv_epilogue_t* epilogue, const sessd_tile_list_t* list,
+                                 hipStream_t stream) {
   if (cin < 16 || cin % 16 || batch < 1 || cout < 1 || hout < 2 || wout < 2 || (hout & 1) || (wout & 1)) return SESSD_EINVAL;
   if ((hin != 2 * hout && hin != 2 * hout - 1) || (win != 2 * wout && win != 2 * wout - 1)) return SESSD_EINVAL;
-  if (!in || !wsplit || !out || !tile_list || !n_list || list_cap < 1) return SESSD_EINVAL;
+  if (!in || !wsplit || !out || !list || !sessd_tile_list_ok(list)) return SESSD_EINVAL;
   if ((long long)batch * cout * hout * wout * 4 >= 0x7fffffffLL || (long long)batch * cin * hin * win * 4 >= 0x7fffffffLL) return SESSD_EINVAL;
   if (split_pack_bytes(cin, cout) >= 0x7fffffffULL) return SESSD_EINVAL;
   ConvS2SplitArgs A;
-  A.in = in; A.w = wsplit; A.out = out; A.scale = scale; A.shift = shift; A.residual = residual;
-  A.tile_list = tile_list; A.n_list = n_list; A.list_cap = list_cap;
-  A.batch = batch; A.cin = cin; A.hin = hin; A.win = win; A.cout = cout; A.hout = hout; A.wout = wout; A.relu = relu;
+  A.in = in; A.w = wsplit; A.out = out;
+  sessd_take_epilogue(A, epilogue);
+  sessd_take_tile_list(A, list);
+  A.batch = batch; A.cin = cin; A.hin = hin; A.win = win; A.cout = cout; A.hout = hout; A.wout = wout;
   A.ngroups = sessd_divup(cout, 128);
-  const long long wgs = (long long)sessd_divup(list_cap, 16) * A.ngroups;
+  const long long wgs = (long long)sessd_divup(list->cap, 16) * A.ngroups;
   if (wgs > 0x7fffffffLL) return SESSD_EINVAL;
   SESSD_LAUNCH(conv_s2_split_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, A);
   SESSD_CHECK_LAUNCH();

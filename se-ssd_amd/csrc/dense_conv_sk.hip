@@ -492,71 +492,6 @@ int default_workgroups(int* out) {
   return *out >= 8 ? SESSD_OK : SESSD_EINVAL;
 }
 
-int launch_conv2d_sk(const float* in, int batch, int cin, int hin, int win, int nclass, const float* const* wpk,
-                     const int* ntaps, const int* taps_dy, const int* taps_dx, int in_mul, int tile_h, int tile_w, float* out,
-                     int cout, int hout, int wout, int out_mul, const int* out_py, const int* out_px, const float* scale,
-                     const float* shift, int relu, const float* residual, void* workspace, size_t workspace_bytes, int workgroups,
-                     hipStream_t stream, const int* tile_list, const int* n_list, int list_cap, int min_rounds) {
-  if (batch < 1 || cin < 16 || cin % 16 || cout < 1 || nclass < 1 || nclass > 4 || workgroups < 0 || (workgroups & 7)) return SESSD_EINVAL;
-  // a batch element's input and output are addressed through 32-bit buffer offsets
-  if ((long long)cin * hin * win * 4 >= 0x7fffffffLL || (long long)cout * hout * wout * 4 >= 0x7fffffffLL) return SESSD_EINVAL;
-  // active-tile mode: the image is part of the offsets too, and the tile space is cut into 2x2 tiles
-  if (tile_list && (!n_list || list_cap < 1 || (tile_h & 1) || (tile_w & 1) || (long long)batch * cin * hin * win * 4 >= 0x7fffffffLL ||
-                    (long long)batch * cout * hout * wout * 4 >= 0x7fffffffLL))
-    return SESSD_EINVAL;
-  if (workgroups == 0) {
-    const int rc = default_workgroups(&workgroups);
-    if (rc != SESSD_OK) return rc;
-  }
-  SkArgs A;
-  A.in = in; A.out = out; A.scale = scale; A.shift = shift; A.residual = residual;
-  A.cin = cin; A.hin = hin; A.win = win; A.cout = cout; A.hout = hout; A.wout = wout; A.wt = tile_w;
-  A.in_mul = in_mul; A.out_mul = out_mul; A.relu = relu;
-  A.npix = tile_h * tile_w; A.ptiles = sessd_divup(A.npix, 128); A.cgroups = sessd_divup(cout, 128); A.ncb = cin / 16;
-  A.batch = batch; A.nclass = nclass;
-  A.tile_list = tile_list; A.n_list = n_list; A.list_cap = list_cap; A.min_rounds = min_rounds < 1 ? 1 : min_rounds;
-  A.ntiles2 = (tile_h / 2) * (tile_w / 2); A.tw2 = tile_w / 2;
-  // the round list: for every (batch element, pixel tile, cout group) the units of all classes one after the other (more taps
-  // first) -- the classes of a pixel tile read the same input and write the interleaved pixels of the same output lines, and
-  // consecutive shares run on the same XCD: the input is fetched once and the half-written output lines meet in that L2
-  int order[4] = {0, 1, 2, 3};
-  for (int a = 0; a < nclass; ++a)
-    for (int b = a + 1; b < nclass; ++b)
-      if (ntaps[order[b]] > ntaps[order[a]]) { const int t = order[a]; order[a] = order[b]; order[b] = t; }
-  const long long groups = (long long)batch * A.ptiles * A.cgroups;  // (batch element, pixel tile, cout group)
-  int rpg = 0;
-  for (int k = 0; k < nclass; ++k) {
-    const int c = order[k];
-    if (ntaps[c] < 1 || ntaps[c] > 9) return SESSD_EINVAL;
-    SkClass& C = A.cls[k];
-    C.wpk = wpk[c]; C.ntaps = ntaps[c]; C.py = out_py[c]; C.px = out_px[c];
-    C.rpu = ntaps[c] * A.ncb;
-    C.r_begin = rpg; C.u_begin = 0;
-    for (int t = 0; t < 9; ++t) {
-      C.dy[t] = t < ntaps[c] ? taps_dy[9 * c + t] : 0;
-      C.dx[t] = t < ntaps[c] ? taps_dx[9 * c + t] : 0;
-    }
-    rpg += C.rpu;
-  }
-  for (int k = nclass; k < 4; ++k) A.cls[k] = A.cls[0];
-  A.rpg = rpg;
-  const long long rounds = groups * rpg;
-  if (rounds > 0x7fffffffLL || groups * nclass > 0x7fffffffLL) return SESSD_EINVAL;
-  A.total_rounds = (int)rounds;
-  const size_t cbytes = sessd_align((size_t)groups * nclass * 4, 256);
-  if (cbytes + (size_t)2 * workgroups * CSK_SLOT_BYTES > workspace_bytes) return SESSD_EWORKSPACE;
-  // every share must hold at least one round (the part count of a cut unit is a difference of share indices)
-  if (workgroups > A.total_rounds) workgroups = A.total_rounds >= 8 ? (A.total_rounds & ~7) : A.total_rounds;
-  A.counters = (unsigned*)workspace;
-  A.scratch = (float*)((char*)workspace + cbytes);
-  if (tile_list)   // (shares are sized on the device: the workspace and the launch are the dense layer's)
-    SESSD_LAUNCH((conv2d_sk_kernel<true>), dim3(workgroups), dim3(256), 0, stream, A);
-  else
-    SESSD_LAUNCH((conv2d_sk_kernel<false>), dim3(workgroups), dim3(256), 0, stream, A);
-  SESSD_CHECK_LAUNCH();
-  return SESSD_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -590,32 +525,80 @@ int sessd_conv2d_sk_pack(const float* w, long long out_stride, long long in_stri
 // launch: a Conv2d (nclass 1: 3x3 or 1x1, any stride via in_mul) or the four output-parity classes of the stride-2 transposed
 // conv. Class c: wpk[c] (device, sessd_conv2d_sk_pack), ntaps[c] <= 9 taps with input offsets taps_dy/dx[9 c + t] (host ints),
 // output pixel (y * out_mul + out_py[c], x * out_mul + out_px[c]) for tile-space pixel (y, x) of tile_h x tile_w, input pixel
-// (y * in_mul + dy, x * in_mul + dx). cin % 16 == 0. workgroups: a multiple of 8, 0 = one per CU.
+// (y * in_mul + dy, x * in_mul + dx). cin % 16 == 0. sk->workgroups: a multiple of 8, 0 = one per CU.
+// list != NULL: the same launch over the listed 2x2 tiles of the TILE SPACE only (active-tile mode, csrc/dense_active.hip: the BEV
+// maps of the SSFA neck are a per-channel constant away from the sparse sites): tiles[0 .. min(*count, cap)) entries image *
+// (tile_h/2 * tile_w/2) + tile in any order; every class is computed at the four tile-space pixels of a listed tile, the other
+// output pixels are left alone (sessd_fill_inactive_tiles writes the layer's constant there). Even tile_h, tile_w. Shares of the
+// round list are at least sk->min_rounds rounds long; the workgroups beyond rounds / min_rounds leave at once. Same packed weights,
+// same workspace (sized for the dense layer) as the whole-map launch.
 int sessd_conv2d_sk(const float* in, int batch, int cin, int hin, int win, int nclass, const float* const* wpk,
                     const int* ntaps, const int* taps_dy, const int* taps_dx, int in_mul, int tile_h, int tile_w, float* out,
-                    int cout, int hout, int wout, int out_mul, const int* out_py, const int* out_px, const float* scale,
-                    const float* shift, int relu, const float* residual, void* workspace, size_t workspace_bytes, int workgroups,
+                    int cout, int hout, int wout, int out_mul, const int* out_py, const int* out_px,
+                    const sessd_conv_epilogue_t* epilogue, const sessd_tile_list_t* list, const sessd_stream_k_t* sk,
                     hipStream_t stream) {
-  return launch_conv2d_sk(in, batch, cin, hin, win, nclass, wpk, ntaps, taps_dy, taps_dx, in_mul, tile_h, tile_w, out, cout, hout, wout,
-                          out_mul, out_py, out_px, scale, shift, relu, residual, workspace, workspace_bytes, workgroups, stream, nullptr,
-                          nullptr, 0, 1);
-}
-
-// The same launch over the listed 2x2 tiles of the TILE SPACE only (active-tile mode, csrc/dense_active.hip: the BEV maps of the
-// SSFA neck are a per-channel constant away from the sparse sites): tile_list[0 .. min(*n_list, list_cap)) entries image *
-// (tile_h/2 * tile_w/2) + tile in any order, count on the device; every class is computed at the four tile-space pixels of a
-// listed tile, the other output pixels are left alone (sessd_fill_inactive_tiles writes the layer's constant there). Even tile_h,
-// tile_w. Shares of the round list are at least min_rounds rounds long; the workgroups beyond rounds / min_rounds leave at once.
-// Same packed weights, same workspace (sized for the dense layer) as sessd_conv2d_sk.
-int sessd_conv2d_sk_active(const float* in, int batch, int cin, int hin, int win, int nclass, const float* const* wpk,
-                           const int* ntaps, const int* taps_dy, const int* taps_dx, int in_mul, int tile_h, int tile_w, float* out,
-                           int cout, int hout, int wout, int out_mul, const int* out_py, const int* out_px, const float* scale,
-                           const float* shift, int relu, const float* residual, const int32_t* tile_list, const int32_t* n_list,
-                           int list_cap, int min_rounds, void* workspace, size_t workspace_bytes, int workgroups, hipStream_t stream) {
-  if (!tile_list || !n_list || list_cap < 1) return SESSD_EINVAL;
-  return launch_conv2d_sk(in, batch, cin, hin, win, nclass, wpk, ntaps, taps_dy, taps_dx, in_mul, tile_h, tile_w, out, cout, hout, wout,
-                          out_mul, out_py, out_px, scale, shift, relu, residual, workspace, workspace_bytes, workgroups, stream, tile_list,
-                          n_list, list_cap, min_rounds);
+  if (!sk) return SESSD_EINVAL;
+  int workgroups = sk->workgroups;
+  if (batch < 1 || cin < 16 || cin % 16 || cout < 1 || nclass < 1 || nclass > 4 || workgroups < 0 || (workgroups & 7)) return SESSD_EINVAL;
+  // a batch element's input and output are addressed through 32-bit buffer offsets
+  if ((long long)cin * hin * win * 4 >= 0x7fffffffLL || (long long)cout * hout * wout * 4 >= 0x7fffffffLL) return SESSD_EINVAL;
+  // active-tile mode: the image is part of the offsets too, and the tile space is cut into 2x2 tiles
+  if (list && (!sessd_tile_list_ok(list) || (tile_h & 1) || (tile_w & 1) ||
+               (long long)batch * cin * hin * win * 4 >= 0x7fffffffLL || (long long)batch * cout * hout * wout * 4 >= 0x7fffffffLL))
+    return SESSD_EINVAL;
+  if (workgroups == 0) {
+    const int rc = default_workgroups(&workgroups);
+    if (rc != SESSD_OK) return rc;
+  }
+  SkArgs A;
+  A.in = in; A.out = out;
+  sessd_take_epilogue(A, epilogue);
+  A.cin = cin; A.hin = hin; A.win = win; A.cout = cout; A.hout = hout; A.wout = wout; A.wt = tile_w;
+  A.in_mul = in_mul; A.out_mul = out_mul;
+  A.npix = tile_h * tile_w; A.ptiles = sessd_divup(A.npix, 128); A.cgroups = sessd_divup(cout, 128); A.ncb = cin / 16;
+  A.batch = batch; A.nclass = nclass;
+  sessd_take_tile_list(A, list);
+  A.min_rounds = list && sk->min_rounds > 1 ? sk->min_rounds : 1;
+  A.ntiles2 = (tile_h / 2) * (tile_w / 2); A.tw2 = tile_w / 2;
+  // the round list: for every (batch element, pixel tile, cout group) the units of all classes one after the other (more taps
+  // first) -- the classes of a pixel tile read the same input and write the interleaved pixels of the same output lines, and
+  // consecutive shares run on the same XCD: the input is fetched once and the half-written output lines meet in that L2
+  int order[4] = {0, 1, 2, 3};
+  for (int a = 0; a < nclass; ++a)
+    for (int b = a + 1; b < nclass; ++b)
+      if (ntaps[order[b]] > ntaps[order[a]]) { const int t = order[a]; order[a] = order[b]; order[b] = t; }
+  const long long groups = (long long)batch * A.ptiles * A.cgroups;  // (batch element, pixel tile, cout group)
+  int rpg = 0;
+  for (int k = 0; k < nclass; ++k) {
+    const int c = order[k];
+    if (ntaps[c] < 1 || ntaps[c] > 9) return SESSD_EINVAL;
+    SkClass& C = A.cls[k];
+    C.wpk = wpk[c]; C.ntaps = ntaps[c]; C.py = out_py[c]; C.px = out_px[c];
+    C.rpu = ntaps[c] * A.ncb;
+    C.r_begin = rpg; C.u_begin = 0;
+    for (int t = 0; t < 9; ++t) {
+      C.dy[t] = t < ntaps[c] ? taps_dy[9 * c + t] : 0;
+      C.dx[t] = t < ntaps[c] ? taps_dx[9 * c + t] : 0;
+    }
+    rpg += C.rpu;
+  }
+  for (int k = nclass; k < 4; ++k) A.cls[k] = A.cls[0];
+  A.rpg = rpg;
+  const long long rounds = groups * rpg;
+  if (rounds > 0x7fffffffLL || groups * nclass > 0x7fffffffLL) return SESSD_EINVAL;
+  A.total_rounds = (int)rounds;
+  const size_t cbytes = sessd_align((size_t)groups * nclass * 4, 256);
+  if (cbytes + (size_t)2 * workgroups * CSK_SLOT_BYTES > sk->workspace_bytes) return SESSD_EWORKSPACE;
+  // every share must hold at least one round (the part count of a cut unit is a difference of share indices)
+  if (workgroups > A.total_rounds) workgroups = A.total_rounds >= 8 ? (A.total_rounds & ~7) : A.total_rounds;
+  A.counters = (unsigned*)sk->workspace;
+  A.scratch = (float*)((char*)sk->workspace + cbytes);
+  if (list)   // (shares are sized on the device: the workspace and the launch are the dense layer's)
+    SESSD_LAUNCH((conv2d_sk_kernel<true>), dim3(workgroups), dim3(256), 0, stream, A);
+  else
+    SESSD_LAUNCH((conv2d_sk_kernel<false>), dim3(workgroups), dim3(256), 0, stream, A);
+  SESSD_CHECK_LAUNCH();
+  return SESSD_OK;
 }
 
 }  // extern "C"

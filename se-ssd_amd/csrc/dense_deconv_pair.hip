@@ -189,14 +189,14 @@ __global__ __launch_bounds__(NW * 64) void deconv_s2_pair_kernel(DeconvPairArgs 
 // feeds two cout tiles, 4 operand loads per 3 MFMAs) was measured slower (236 registers, half the waves in flight).
 // Called by sessd_deconv2d_s2_mfma (dense_conv.hip) for tile_cfg 40 + variant; wpk4 in class order (0,0),(0,1),(1,0),(1,1).
 int sessd_deconv_pair_launch(const float* in, int batch, int cin, int hin, int win, const float* const* wpk4, float* out, int cout,
-                             const float* scale, const float* shift, int relu, const float* residual, int variant,
-                             hipStream_t stream) {
+                             const sessd_conv_epilogue_t* epilogue, int variant, hipStream_t stream) {
   if (cin % 4 || batch < 1 || cout < 1 || variant < 0 || variant > 2) return SESSD_EINVAL;
   if ((size_t)cout * 4 * hin * win * 4 > 0x7fffffffULL || (size_t)cin * hin * win * 4 > 0x7fffffffULL) return SESSD_EINVAL;
   DeconvPairArgs A;
-  A.in = in; A.out = out; A.scale = scale; A.shift = shift; A.residual = residual;
+  A.in = in; A.out = out;
+  sessd_take_epilogue(A, epilogue);
   for (int c = 0; c < 4; ++c) A.w[c] = wpk4[c];
-  A.cin = cin; A.hin = hin; A.win = win; A.cout = cout; A.cout_pad = sessd_divup(cout, 32) * 32; A.relu = relu;
+  A.cin = cin; A.hin = hin; A.win = win; A.cout = cout; A.cout_pad = sessd_divup(cout, 32) * 32;
   static const int nw[3] = {4, 2, 1};
   dim3 grid(sessd_divup(hin * win, nw[variant] * 32) * (A.cout_pad / 32), 1, batch * 2);
   switch (variant) {

@@ -337,27 +337,27 @@ size_t split_pack_bytes(int cin, int cout) { return (size_t)sessd_divup(cout, 12
 
 extern "C" {
 
-// The two ConvTranspose2d(cin, cout, 3, 2, 1, 1) layers of sessd_deconv2d_s2_mfma_pair_active over the same tile list, on the
+// The two ConvTranspose2d(cin, cout, 3, 2, 1, 1) layers of sessd_deconv2d_s2_mfma_pair over the same tile list, on the
 // bf16 matrix cores with three-way split operands (f32 accuracy). wsplit_a / wsplit_b: each layer's weight as three bf16 planes
 // in fragment order (ops.pack_deconv2d_s2(w).wsplit(): ceil(cout / 128) * cin / 16 * 27 * 4096 bytes); the tap tables are
 // the fixed ones of a stride-2 3x3 transposed conv. cin % 16 == 0, even hin / win, the whole batch inside 32-bit offsets.
 // One workgroup of 4 waves per (16 list entries, 128 couts, layer), two per CU; no scratch (resources in the header above).
 int sessd_deconv2d_s2_pair_split_active(const float* in, int batch, int cin, int hin, int win, const void* wsplit_a, const void* wsplit_b,
-                                        float* out_a, float* out_b, int cout, const float* scale_a, const float* shift_a,
-                                        const float* scale_b, const float* shift_b, int relu, const float* residual_a,
-                                        const float* residual_b, const int32_t* tile_list, const int32_t* n_list, int list_cap,
-                                        hipStream_t stream) {
+                                        float* out_a, float* out_b, int cout, const sessd_conv_epilogue_t* epilogue_a,
+                                        const sessd_conv_epilogue_t* epilogue_b, const sessd_tile_list_t* list, hipStream_t stream) {
   if (cin < 16 || cin % 16 || batch < 1 || cout < 1 || hin < 2 || win < 2 || (hin & 1) || (win & 1)) return SESSD_EINVAL;
-  if (!in || !wsplit_a || !wsplit_b || !out_a || !out_b || !tile_list || !n_list || list_cap < 1) return SESSD_EINVAL;
+  if (!in || !wsplit_a || !wsplit_b || !out_a || !out_b || !list || !sessd_tile_list_ok(list)) return SESSD_EINVAL;
   if ((long long)batch * cout * 4 * hin * win * 4 >= 0x7fffffffLL || (long long)batch * cin * hin * win * 4 >= 0x7fffffffLL) return SESSD_EINVAL;
   if (split_pack_bytes(cin, cout) >= 0x7fffffffULL) return SESSD_EINVAL;
+  const sessd_conv_epilogue_t none = {nullptr, nullptr, nullptr, 0};
+  const sessd_conv_epilogue_t* e[2] = {epilogue_a ? epilogue_a : &none, epilogue_b ? epilogue_b : &none};
+  if ((e[0]->relu != 0) != (e[1]->relu != 0)) return SESSD_EINVAL;   // the kernel has one activation for both layers
   DeconvSplitArgs A;
   A.in = in; A.w[0] = wsplit_a; A.w[1] = wsplit_b; A.out[0] = out_a; A.out[1] = out_b;
-  A.scale[0] = scale_a; A.scale[1] = scale_b; A.shift[0] = shift_a; A.shift[1] = shift_b;
-  A.residual[0] = residual_a; A.residual[1] = residual_b;
-  A.tile_list = tile_list; A.n_list = n_list; A.list_cap = list_cap;
-  A.batch = batch; A.cin = cin; A.hin = hin; A.win = win; A.cout = cout; A.relu = relu; A.ngroups = sessd_divup(cout, 128);
-  const long long wgs = (long long)sessd_divup(list_cap, 16) * A.ngroups * 2;
+  for (int l = 0; l < 2; ++l) { A.scale[l] = e[l]->scale; A.shift[l] = e[l]->shift; A.residual[l] = e[l]->residual; }
+  sessd_take_tile_list(A, list);
+  A.batch = batch; A.cin = cin; A.hin = hin; A.win = win; A.cout = cout; A.relu = e[0]->relu; A.ngroups = sessd_divup(cout, 128);
+  const long long wgs = (long long)sessd_divup(list->cap, 16) * A.ngroups * 2;
   if (wgs > 0x7fffffffLL) return SESSD_EINVAL;
   SESSD_LAUNCH(deconv_pair_split_kernel<4>, dim3((unsigned)wgs), dim3(256), 0, stream, A);
   SESSD_CHECK_LAUNCH();

@@ -1125,61 +1125,64 @@ __global__ __launch_bounds__(256, 1) void conv3x3s1_winograd_rk_kernel(WinoArgs 
 #undef SESSD_RK_FINISH_PENDING
 }
 
-int launch_rk(const float* in, int batch, int nsets, int cin, int h, int w, const float* upk, float* out, int cout, const float* scale,
-              const float* shift, int relu, const float* residual, void* workspace, size_t workspace_bytes, int workgroups,
-              hipStream_t stream) {
+// workgroups: the stream-K block's count with its default resolved (the same for launch_sk)
+int launch_rk(const float* in, int batch, int nsets, int cin, int h, int w, const float* upk, float* out, int cout,
+              const sessd_conv_epilogue_t* epilogue, const sessd_stream_k_t& sk, int workgroups, hipStream_t stream) {
   constexpr int SLOT = 4 * 32 * 32 * 4;
   if (cin % 16) return SESSD_EINVAL;
   WinoArgs A;
-  A.in = in; A.upk = upk; A.out = out; A.scale = scale; A.shift = shift; A.residual = residual;
-  A.cin = cin; A.hin = h; A.win = w; A.cout = cout; A.relu = relu;
+  A.in = in; A.upk = upk; A.out = out;
+  sessd_take_epilogue(A, epilogue);
+  A.cin = cin; A.hin = h; A.win = w; A.cout = cout;
   A.tw = w / 2; A.ntiles = (h / 2) * (w / 2); A.tblocks = sessd_divup(A.ntiles, 32); A.ngroups = sessd_divup(cout, 128);
   A.rpu = cin / 16;
   A.bper = batch / nsets; A.ss_stride = nsets > 1 ? cout : 0;
   A.upk_stride = nsets > 1 ? (long long)sessd_divup(cout, 128) * (cin >> 1) * (4 * 2 * 32 * 16) : 0;
-  A.tile_list = nullptr; A.n_list = nullptr; A.list_cap = 0; A.min_rounds = 1; A.batch = batch;
+  sessd_take_tile_list(A, nullptr); A.min_rounds = 1; A.batch = batch;
   const long long units = (long long)batch * A.tblocks * A.ngroups;
   if (units * A.rpu > 0x7fffffffLL) return SESSD_EINVAL;
   A.total_rounds = (int)(units * A.rpu);
   const size_t need = sessd_align((size_t)units * 4, 256) + (size_t)2 * workgroups * SLOT * 4;
-  if (need > workspace_bytes) return SESSD_EWORKSPACE;
+  if (need > sk.workspace_bytes) return SESSD_EWORKSPACE;
   if (workgroups > A.total_rounds) workgroups = A.total_rounds >= 8 ? (A.total_rounds & ~7) : A.total_rounds;
-  A.counters = (unsigned*)workspace;
-  A.scratch = (float*)((char*)workspace + sessd_align((size_t)units * 4, 256));
+  A.counters = (unsigned*)sk.workspace;
+  A.scratch = (float*)((char*)sk.workspace + sessd_align((size_t)units * 4, 256));
   SESSD_LAUNCH((conv3x3s1_winograd_rk_kernel<0>), dim3(workgroups), dim3(256), 0, stream, A);
   SESSD_CHECK_LAUNCH();
   return SESSD_OK;
 }
 
 template <int NW, int CBN, bool SPLIT = false>
-int launch_sk(const float* in, int batch, int nsets, int cin, int h, int w, const float* upk, float* out, int cout, const float* scale,
-              const float* shift, int relu, const float* residual, void* workspace, size_t workspace_bytes, int workgroups,
-              hipStream_t stream, const int* tile_list = nullptr, const int* n_list = nullptr, int list_cap = 0, int min_rounds = 1) {
+int launch_sk(const float* in, int batch, int nsets, int cin, int h, int w, const float* upk, float* out, int cout,
+              const sessd_conv_epilogue_t* epilogue, const sessd_tile_list_t* list, const sessd_stream_k_t& sk, int workgroups,
+              hipStream_t stream) {
   constexpr int SLOT = CBN * 32 * 32 * 4;
   if (cin % (2 * NW)) return SESSD_EINVAL;
-  if (tile_list && (nsets != 1 || !n_list || list_cap < 1 || (size_t)batch * cin * h * w * 4 >= 0xFFFFFFFFull)) return SESSD_EINVAL;
   WinoArgs A;
-  A.in = in; A.upk = upk; A.out = out; A.scale = scale; A.shift = shift; A.residual = residual;
-  A.cin = cin; A.hin = h; A.win = w; A.cout = cout; A.relu = relu;
+  sessd_take_tile_list(A, list);   // (checked by the entry)
+  A.in = in; A.upk = upk; A.out = out;
+  sessd_take_epilogue(A, epilogue);
+  A.cin = cin; A.hin = h; A.win = w; A.cout = cout;
   A.tw = w / 2; A.ntiles = (h / 2) * (w / 2); A.tblocks = sessd_divup(A.ntiles, 32); A.ngroups = sessd_divup(cout, CBN * 32);
   A.rpu = cin / (2 * NW);
   A.bper = batch / nsets; A.ss_stride = nsets > 1 ? cout : 0;
   A.upk_stride = nsets > 1 ? (long long)sessd_divup(cout, CBN * 32) * (cin >> 1) * (NW * 2 * 32 * 32 / 4) : 0;
   if (SPLIT && nsets > 1) A.upk_stride = (long long)sessd_divup(cout, CBN * 32) * cin * 3072;  // three bf16 planes: 1.5 x the f32 bytes
   // min_rounds < 0 (list launches only): whole-unit shares, at least -min_rounds units per workgroup
-  A.tile_list = tile_list; A.n_list = n_list; A.list_cap = list_cap; A.min_rounds = (min_rounds < 0 && tile_list) ? min_rounds : (min_rounds < 1 ? 1 : min_rounds); A.batch = batch;
+  const int min_rounds = list ? sk.min_rounds : 1;
+  A.min_rounds = min_rounds < 0 ? min_rounds : (min_rounds < 1 ? 1 : min_rounds); A.batch = batch;
   const long long units = (long long)batch * A.tblocks * A.ngroups;
   if (units * A.rpu > 0x7fffffffLL) return SESSD_EINVAL;
   A.total_rounds = (int)(units * A.rpu);
   const size_t need = sessd_align((size_t)units * 4, 256) + (size_t)2 * workgroups * SLOT * 4;
-  if (need > workspace_bytes) return SESSD_EWORKSPACE;
+  if (need > sk.workspace_bytes) return SESSD_EWORKSPACE;
   // every share must hold at least one round (the part count of a cut unit is a difference of share indices)
   if (workgroups > A.total_rounds) workgroups = A.total_rounds >= 8 ? (A.total_rounds & ~7) : A.total_rounds;
-  A.counters = (unsigned*)workspace;
-  A.scratch = (float*)((char*)workspace + sessd_align((size_t)units * 4, 256));
+  A.counters = (unsigned*)sk.workspace;
+  A.scratch = (float*)((char*)sk.workspace + sessd_align((size_t)units * 4, 256));
   static const int var = [] { const char* e = getenv("SESSD_WINO_VAR"); return e ? atoi(e) & 7 : 0; }();
   if constexpr (SPLIT) {   // bits 0 and 1 are the f32 loop's
-    if (tile_list) {
+    if (list) {
       if (var & 4) SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 4, true, true>), dim3(workgroups), dim3(NW * 64), 0, stream, A);
       else SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 0, true, true>), dim3(workgroups), dim3(NW * 64), 0, stream, A);
     } else {
@@ -1189,7 +1192,7 @@ int launch_sk(const float* in, int batch, int nsets, int cin, int h, int w, cons
     SESSD_CHECK_LAUNCH();
     return SESSD_OK;
   }
-  if (tile_list) {   // active-tile mode: the same kernel over a device list of tiles (shares are sized on the device)
+  if (list) {   // active-tile mode: the same kernel over a device list of tiles (shares are sized on the device)
     SESSD_LAUNCH((conv3x3s1_winograd_sk_kernel<NW, CBN, 0, true, false>), dim3(workgroups), dim3(NW * 64), 0, stream, A);
     SESSD_CHECK_LAUNCH();
     return SESSD_OK;
@@ -1229,64 +1232,39 @@ size_t sessd_conv3x3_winograd_sk_workspace_bytes(int batch, int h, int w, int co
 }
 
 // Conv2d(cin, cout, 3, stride 1, padding 1) + folded BatchNorm + ReLU + residual, fused Winograd F(2x2,3x3), stream-K over
-// `workgroups` persistent workgroups (a multiple of 8; 0 = the shape's default).
+// sk->workgroups persistent workgroups (a multiple of 8; 0 = the shape's default).
 // upk = U = G g G^T packed [ceil(cout / C)][cin/2][NW][2][32][C/32][16/NW] with (NW, C) = (8, 128) for shape 0, (4, 64) for
 // shape 1; shape 3: three bf16 planes [ceil(cout / 128)][wave 8][cin/2 steps][3][64][8] (ops.pack_winograd_sk); even H, W;
 // cin % (2 NW) == 0.
-// Several layers of ONE shape in one launch (conv_0 / conv_1 of the SSFA neck, rpn_v1.py:201-210): the batch dimension is
-// nsets consecutive groups of batch / nsets elements, group s convolved with weight set s -- upk = nsets packings back to back,
+// nsets > 1, several layers of ONE shape in one launch (conv_0 / conv_1 of the SSFA neck, rpn_v1.py:201-210): the batch dimension
+// is nsets consecutive groups of batch / nsets elements, group s convolved with weight set s -- upk = nsets packings back to back,
 // scale / shift = nsets x cout. One round list, one pipeline fill and one tail instead of nsets.
-int sessd_conv3x3_winograd_sk_sets(const float* in, int batch, int nsets, int cin, int h, int w, const float* upk, float* out,
-                                   int cout, const float* scale, const float* shift, int relu, const float* residual,
-                                   void* workspace, size_t workspace_bytes, int shape, int workgroups, hipStream_t stream) {
-  if ((h & 1) || (w & 1) || batch < 1 || nsets < 1 || batch % nsets || cout < 1 || workgroups < 0 || (workgroups & 7) || shape < 0 ||
-      shape > 3)
+// list != NULL, ACTIVE-TILE mode of the same kernel (the first layers of the SSFA neck, rpn_v1.py:135-160, on a BEV map that is
+// zero outside the sparse backbone's sites; nsets 1, shape 0, 1 or 3): only the 2x2-output tiles listed in tiles[0 .. min(*count,
+// cap)) are computed and written -- entries image * (h/2 * w/2) + tile in any fixed order (sessd_bev_tile_activity builds both).
+// The other tiles of `out` are the caller's (sessd_fill_inactive_tiles writes the layer's constant there). Workgroups beyond
+// rounds / sk->min_rounds leave at once. min_rounds = -k: WHOLE-UNIT shares -- every workgroup takes at least k whole units (32
+// tiles x the shape's couts x all input channels), nothing is cut, the scratch slots stay untouched. Same packed U, same workspace
+// (sized for the dense layer) as the whole-map launch.
+int sessd_conv3x3_winograd_sk(const float* in, int batch, int nsets, int cin, int h, int w, const float* upk, float* out, int cout,
+                              const sessd_conv_epilogue_t* epilogue, const sessd_tile_list_t* list, const sessd_stream_k_t* sk,
+                              int shape, hipStream_t stream) {
+  if ((h & 1) || (w & 1) || batch < 1 || nsets < 1 || batch % nsets || cout < 1 || !sk || sk->workgroups < 0 || (sk->workgroups & 7) ||
+      shape < 0 || shape > 3)
     return SESSD_EINVAL;
+  // a list launch: one weight set, not the register-transform shape, the image part of the input's 32-bit offsets
+  if (list && (!sessd_tile_list_ok(list) || nsets != 1 || shape == 2 || (size_t)batch * cin * h * w * 4 >= 0xFFFFFFFFull))
+    return SESSD_EINVAL;
+  int workgroups = sk->workgroups;
   if (workgroups == 0) {
     const int rc = default_workgroups(shape, &workgroups);
     if (rc != SESSD_OK) return rc;
   }
   if (shape == 2)   // third generation: output transform in registers (same cuts and bits as shape 0)
-    return launch_rk(in, batch, nsets, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace, workspace_bytes, workgroups, stream);
-  if (shape == 1)
-    return launch_sk<4, 2>(in, batch, nsets, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace, workspace_bytes, workgroups, stream);
-  if (shape == 3)
-    return launch_sk<8, 4, true>(in, batch, nsets, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace, workspace_bytes, workgroups, stream);
-  return launch_sk<8, 4>(in, batch, nsets, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace, workspace_bytes, workgroups, stream);
-}
-
-// ACTIVE-TILE mode of the same kernel (round 4; the first layers of the SSFA neck, rpn_v1.py:135-160, on a BEV map that is zero
-// outside the sparse backbone's sites): only the 2x2-output tiles listed in tile_list[0 .. min(*n_list, list_cap)) are computed
-// and written -- entries image * (h/2 * w/2) + tile in any fixed order, count on the device (sessd_bev_tile_activity builds both).
-// The other tiles of `out` are the caller's (sessd_fill_inactive_tiles writes the layer's constant there). Workgroups beyond
-// rounds / min_rounds leave at once. min_rounds = -k (round 5): WHOLE-UNIT shares -- every workgroup takes at least k whole
-// units (32 tiles x the shape's couts x all input channels), nothing is cut, the scratch slots stay untouched. Same packed U, same workspace (sized for the dense layer) as sessd_conv3x3_winograd_sk.
-int sessd_conv3x3_winograd_sk_active(const float* in, int batch, int cin, int h, int w, const float* upk, float* out, int cout,
-                                     const float* scale, const float* shift, int relu, const float* residual,
-                                     const int32_t* tile_list, const int32_t* n_list, int list_cap, int min_rounds, void* workspace,
-                                     size_t workspace_bytes, int shape, int workgroups, hipStream_t stream) {
-  if ((h & 1) || (w & 1) || batch < 1 || cout < 1 || workgroups < 0 || (workgroups & 7) || shape < 0 || shape > 3 || shape == 2 ||
-      !tile_list || !n_list || list_cap < 1)
-    return SESSD_EINVAL;
-  if (workgroups == 0) {
-    const int rc = default_workgroups(shape, &workgroups);
-    if (rc != SESSD_OK) return rc;
-  }
-  if (shape == 1)
-    return launch_sk<4, 2>(in, batch, 1, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace, workspace_bytes, workgroups,
-                           stream, tile_list, n_list, list_cap, min_rounds);
-  if (shape == 3)
-    return launch_sk<8, 4, true>(in, batch, 1, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace, workspace_bytes,
-                                 workgroups, stream, tile_list, n_list, list_cap, min_rounds);
-  return launch_sk<8, 4>(in, batch, 1, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace, workspace_bytes, workgroups,
-                         stream, tile_list, n_list, list_cap, min_rounds);
-}
-
-int sessd_conv3x3_winograd_sk(const float* in, int batch, int cin, int h, int w, const float* upk, float* out, int cout,
-                              const float* scale, const float* shift, int relu, const float* residual, void* workspace,
-                              size_t workspace_bytes, int shape, int workgroups, hipStream_t stream) {
-  return sessd_conv3x3_winograd_sk_sets(in, batch, 1, cin, h, w, upk, out, cout, scale, shift, relu, residual, workspace,
-                                        workspace_bytes, shape, workgroups, stream);
+    return launch_rk(in, batch, nsets, cin, h, w, upk, out, cout, epilogue, *sk, workgroups, stream);
+  if (shape == 1) return launch_sk<4, 2>(in, batch, nsets, cin, h, w, upk, out, cout, epilogue, list, *sk, workgroups, stream);
+  if (shape == 3) return launch_sk<8, 4, true>(in, batch, nsets, cin, h, w, upk, out, cout, epilogue, list, *sk, workgroups, stream);
+  return launch_sk<8, 4>(in, batch, nsets, cin, h, w, upk, out, cout, epilogue, list, *sk, workgroups, stream);
 }
 
 }  // extern "C"

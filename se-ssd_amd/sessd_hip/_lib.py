@@ -17,7 +17,6 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libsessd_hip.so")
 vp, i32, u32, f32, sz, i64, f64 = C.c_void_p, C.c_int, C.c_uint32, C.c_float, C.c_size_t, C.c_longlong, C.c_double
 
 
-
 class ChainLevel(C.Structure):
     """sessd_chain_level_t (include/sessd_hip_types.h)"""
     _fields_ = [("ksize", i32 * 3), ("stride", i32 * 3), ("pad", i32 * 3), ("out_dims", i32 * 3), ("cap", i32),
@@ -64,6 +63,24 @@ class PredictArgs(C.Structure):
                 ("record_counts", vp), ("capacity_frames", i32), ("cursor", vp), ("di", C.POINTER(DiCfg)), ("di_truncated", vp),
                 ("di_truncated_sticky", vp), ("di_keep", vp), ("di_keep_count", vp)]
 
+
+class ConvEpilogue(C.Structure):
+    """sessd_conv_epilogue_t (include/sessd_hip_types.h)"""
+    _fields_ = [("scale", vp), ("shift", vp), ("residual", vp), ("relu", i32)]
+
+
+class TileList(C.Structure):
+    """sessd_tile_list_t (include/sessd_hip_types.h)"""
+    _fields_ = [("tiles", vp), ("count", vp), ("cap", i32)]
+
+
+class StreamK(C.Structure):
+    """sessd_stream_k_t (include/sessd_hip_types.h)"""
+    _fields_ = [("workspace", vp), ("workspace_bytes", sz), ("workgroups", i32), ("min_rounds", i32)]
+
+
+# the dense launch entries' argument groups: host pointers to the three structs above (None = NULL)
+epi, tl, skp = C.POINTER(ConvEpilogue), C.POINTER(TileList), C.POINTER(StreamK)
 
 # name -> (restype, argtypes). Kept in step with include/sessd_hip.h (tests/test_abi.py checks it).
 SIGNATURES = {
@@ -120,32 +137,22 @@ SIGNATURES = {
     "sessd_nms_workspace_bytes": (sz, [i32]),
     "sessd_nms_sorted": (i32, [i32, vp, i32, f32, vp, vp, vp, sz, vp]),
     "sessd_nms_axis_eps_sorted": (i32, [vp, i32, i32, f32, f32, vp, vp, vp, sz, vp]),
-    "sessd_conv2d_mfma": (i32, [vp, i32, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32,
-                                vp, vp, i32, vp, i32, vp]),
-    "sessd_conv3x3_winograd": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp]),
+    "sessd_conv2d_mfma": (i32, [vp, i32, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, epi, tl, i32, vp]),
+    "sessd_conv3x3_winograd": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, epi, i32, vp]),
     "sessd_conv2d_pack_taps": (i32, [vp, i64, i64, vp, i32, i32, i32, vp, vp]),
     "sessd_conv3x3_winograd_pack": (i32, [vp, i64, i64, i32, i32, i32, i32, vp, vp]),
     "sessd_conv3x3_winograd_sk_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
-    "sessd_conv3x3_winograd_sk_sets": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, sz, i32, i32, vp]),
-    "sessd_conv3x3_winograd_sk": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, sz, i32, i32, vp]),
-    "sessd_conv3x3_winograd_sk_active": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, vp, sz, i32, i32, vp]),
+    "sessd_conv3x3_winograd_sk": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, epi, tl, skp, i32, vp]),
     "sessd_bev_tile_activity_workspace_bytes": (sz, [i32, i32]),
     "sessd_bev_tile_activity": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, sz, vp]),
     "sessd_fill_inactive_tiles": (i32, [vp, i32, i32, vp]),
     "sessd_conv2d_sk_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
     "sessd_conv2d_sk_pack": (i32, [vp, i64, i64, vp, i32, i32, i32, vp, vp]),
-    "sessd_conv2d_sk": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp,
-                              i32, vp, vp, sz, i32, vp]),
-    "sessd_conv2d_sk_active": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp,
-                                     i32, vp, vp, vp, i32, i32, vp, sz, i32, vp]),
-    "sessd_conv2d_mfma_active": (i32, [vp, i32, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp,
-                                       vp, vp, i32, i32, vp]),
-    "sessd_deconv2d_s2_mfma_pair_active": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp,
-                                                 i32, i32, vp]),
-    "sessd_deconv2d_s2_pair_split_active": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]),
-    "sessd_conv2d_s2_split_active": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp]),
-    "sessd_deconv2d_s2_mfma_pair": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp]),
-    "sessd_deconv2d_s2_mfma": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp]),
+    "sessd_conv2d_sk": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, epi, tl, skp, vp]),
+    "sessd_deconv2d_s2_pair_split_active": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, epi, epi, tl, vp]),
+    "sessd_conv2d_s2_split_active": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, epi, tl, vp]),
+    "sessd_deconv2d_s2_mfma_pair": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, epi, epi, tl, i32, vp]),
+    "sessd_deconv2d_s2_mfma": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, epi, i32, vp]),
     "sessd_ssfa_fuse": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, vp, vp]),
     "sessd_ssfa_fuse_head": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
     "sessd_predict_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),

@@ -8,7 +8,7 @@ import os
 
 import torch
 
-from ._lib import lib, check, SessdError
+from ._lib import lib, check, SessdError, ConvEpilogue, TileList, StreamK
 
 
 def _stream():
@@ -1806,88 +1806,107 @@ def conv2d_sk_workspace(batch, tile_h, tile_w, cout, nclass, device, workgroups=
     return torch.zeros(n, dtype=torch.uint8, device=device)
 
 
-def conv2d_winograd_sk_sets(x, upk_sets, nsets, cout, scale, shift, relu, out, shape, workspace, workgroups=0, residual=None):
-    """sessd_conv3x3_winograd_sk_sets: x (nsets * B, Cin, H, W), group s of B batch elements convolved with weight set s.
-    upk_sets = the sets' pack_winograd_sk packings concatenated, scale / shift (nsets, cout) or None; out like x with cout channels."""
+# The three argument groups every dense launch entry takes as structs (include/sessd_hip_types.h); the entries read them before
+# they return, so a temporary is enough.
+def _epilogue(scale, shift, relu, residual):
+    return ConvEpilogue(_p(scale), _p(shift), _p(residual), 1 if relu else 0)
+
+
+def _tile_list(tile_list, n_list):
+    _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
+    return TileList(tile_list.data_ptr(), n_list.data_ptr(), tile_list.numel())
+
+
+def _stream_k(workspace, workgroups, min_rounds=1):
+    return StreamK(workspace.data_ptr(), workspace.numel(), int(workgroups), int(min_rounds))
+
+
+def _winograd_sk(x, nsets, upk, out, cout, epi, tl, sk, shape):
     _req(x, torch.float32, "x")
-    NB, ci, H, W = x.shape
-    check(lib.sessd_conv3x3_winograd_sk_sets(x.data_ptr(), NB, int(nsets), ci, H, W, upk_sets.data_ptr(), out.data_ptr(), int(cout),
-                                             _p(scale), _p(shift), 1 if relu else 0, _p(residual), workspace.data_ptr(),
-                                             workspace.numel(), int(shape), int(workgroups), _stream()), "conv3x3_winograd_sk_sets")
+    B, ci, H, W = x.shape
+    check(lib.sessd_conv3x3_winograd_sk(x.data_ptr(), B, int(nsets), ci, H, W, upk.data_ptr(), out.data_ptr(), int(cout), epi, tl, sk,
+                                        int(shape), _stream()), "conv3x3_winograd_sk")
     return out
+
+
+def conv2d_winograd_sk_sets(x, upk_sets, nsets, cout, scale, shift, relu, out, shape, workspace, workgroups=0, residual=None):
+    """sessd_conv3x3_winograd_sk with nsets weight sets: x (nsets * B, Cin, H, W), group s of B batch elements convolved with set s.
+    upk_sets = the sets' pack_winograd_sk packings concatenated, scale / shift (nsets, cout) or None; out like x with cout channels."""
+    return _winograd_sk(x, nsets, upk_sets, out, cout, _epilogue(scale, shift, relu, residual), None, _stream_k(workspace, workgroups), shape)
 
 
 def conv2d_winograd_sk_active(x, upk, cout, scale, shift, relu, out, shape, workspace, tile_list, n_list, workgroups=0, residual=None,
                               min_rounds=2):
-    """sessd_conv3x3_winograd_sk_active: the stream-K Winograd layer over the listed 2x2-output tiles only (entries image *
+    """sessd_conv3x3_winograd_sk with a tile list: the stream-K Winograd layer over the listed 2x2-output tiles only (entries image *
     (H/2 * W/2) + tile, count on the device: bev_tile_activity); the other tiles of `out` are left alone."""
-    _req(x, torch.float32, "x"); _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
+    return _winograd_sk(x, 1, upk, out, cout, _epilogue(scale, shift, relu, residual), _tile_list(tile_list, n_list),
+                        _stream_k(workspace, workgroups, min_rounds), shape)
+
+
+def _conv2d_sk(x, pc, epi, out, tl, sk, what):
+    """sessd_conv2d_sk (tile_cfg 30) on the layer's argument block pc.sk_args(), over the whole map (tl None) or a tile list"""
+    _req(x, torch.float32, "x")
+    a = pc.sk_args()
+    if a is None:
+        raise ValueError("%s (LDS-tiled stream-K) needs cin % 16 == 0" % what)
     B, ci, H, W = x.shape
-    check(lib.sessd_conv3x3_winograd_sk_active(x.data_ptr(), B, ci, H, W, upk.data_ptr(), out.data_ptr(), int(cout), _p(scale), _p(shift),
-                                               1 if relu else 0, _p(residual), tile_list.data_ptr(), n_list.data_ptr(),
-                                               tile_list.numel(), int(min_rounds), workspace.data_ptr(), workspace.numel(), int(shape),
-                                               int(workgroups), _stream()), "conv3x3_winograd_sk_active")
+    la = pc.launches[0]
+    check(lib.sessd_conv2d_sk(x.data_ptr(), B, ci, H, W, a["n"], _addr(a["wptr"]), _addr(a["ntaps"]), _addr(a["dy"]), _addr(a["dx"]),
+                              la.in_mul, *pc.tile_hw(H, W), out.data_ptr(), pc.cout, *pc.out_hw(H, W), la.out_mul, _addr(a["py"]),
+                              _addr(a["px"]), epi, tl, sk, _stream()), "conv2d_sk")
     return out
 
 
-def _sk_layer_args(x, pc, sk, epi, out):
-    """what sessd_conv2d_sk and sessd_conv2d_sk_active both begin with: the layer (sk = pc.sk_args()), its maps and its epilogue
-    epi = (scale, shift, relu, residual) as the C entries take them"""
-    B, ci, H, W = x.shape
-    la = pc.launches[0]
-    return (x.data_ptr(), B, ci, H, W, sk["n"], _addr(sk["wptr"]), _addr(sk["ntaps"]), _addr(sk["dy"]), _addr(sk["dx"]), la.in_mul,
-            *pc.tile_hw(H, W), out.data_ptr(), pc.cout, *pc.out_hw(H, W), la.out_mul, _addr(sk["py"]), _addr(sk["px"]), *epi)
-
-
 def conv2d_sk_active(x, pc, scale, shift, relu, out, workspace, tile_list, n_list, workgroups=0, residual=None, min_rounds=4):
-    """sessd_conv2d_sk_active: the LDS-tiled stream-K layer (tile_cfg 30: stride-2 / 1x1 conv, or the four classes of a transposed
-    conv) over the listed 2x2 tiles of its tile space only (entries image * (th/2 * tw/2) + tile, count on the device); the other
-    output pixels of `out` are left alone."""
-    _req(x, torch.float32, "x"); _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
-    sk = pc.sk_args()
-    if sk is None:
-        raise ValueError("conv2d_sk_active needs cin % 16 == 0")
-    epi = (_p(scale), _p(shift), 1 if relu else 0, _p(residual))
-    check(lib.sessd_conv2d_sk_active(*_sk_layer_args(x, pc, sk, epi, out), tile_list.data_ptr(), n_list.data_ptr(), tile_list.numel(),
-                                     int(min_rounds), workspace.data_ptr(), workspace.numel(), int(workgroups), _stream()),
-          "conv2d_sk_active")
+    """sessd_conv2d_sk with a tile list: the LDS-tiled stream-K layer (tile_cfg 30: stride-2 / 1x1 conv, or the four classes of a
+    transposed conv) over the listed 2x2 tiles of its tile space only (entries image * (th/2 * tw/2) + tile, count on the device); the
+    other output pixels of `out` are left alone."""
+    return _conv2d_sk(x, pc, _epilogue(scale, shift, relu, residual), out, _tile_list(tile_list, n_list),
+                      _stream_k(workspace, workgroups, min_rounds), "conv2d_sk_active")
+
+
+def _conv2d_mfma(x, pc, la, epi, out, tl, tile_cfg):
+    """sessd_conv2d_mfma: launch `la` of the layer on the direct kernel, over the whole map (tl None) or a tile list"""
+    B, ci, H, W = x.shape
+    check(lib.sessd_conv2d_mfma(x.data_ptr(), B, ci, H, W, la.wpk.data_ptr(), la.ntaps, la.dy.data_ptr(), la.dx.data_ptr(), la.in_mul,
+                                *pc.tile_hw(H, W), out.data_ptr(), pc.cout, *pc.out_hw(H, W), la.out_mul, la.py, la.px, epi, tl,
+                                int(tile_cfg), _stream()), "conv2d_mfma")
     return out
 
 
 def conv2d_mfma_active(x, pc, scale, shift, relu, out, tile_list, n_list, tile_cfg=11, residual=None):
-    """sessd_conv2d_mfma_active: a 1x1 layer on the direct kernel (tile_cfg 3 / 4 / 11 / 12) over the listed 2x2 tiles only; the
-    computed pixels carry the bits of the plain launch."""
-    _req(x, torch.float32, "x"); _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
-    B, ci, H, W = x.shape
-    assert pc.kind == "conv" and pc.stride == 1 and len(pc.launches) == 1 and pc.launches[0].ntaps == 1 and ci % 8 == 0
-    la = pc.launches[0]
-    check(lib.sessd_conv2d_mfma_active(x.data_ptr(), B, ci, H, W, la.wpk.data_ptr(), 1, la.dy.data_ptr(), la.dx.data_ptr(), 1, H, W,
-                                       out.data_ptr(), pc.cout, H, W, 1, 0, 0, _p(scale), _p(shift), 1 if relu else 0, _p(residual),
-                                       tile_list.data_ptr(), n_list.data_ptr(), tile_list.numel(), int(tile_cfg), _stream()),
-          "conv2d_mfma_active")
-    return out
+    """sessd_conv2d_mfma with a tile list: a 1x1 layer on the direct kernel (tile_cfg 3 / 4 / 11 / 12) over the listed 2x2 tiles only;
+    the computed pixels carry the bits of the whole-map launch."""
+    _req(x, torch.float32, "x")
+    assert pc.kind == "conv" and pc.stride == 1 and len(pc.launches) == 1 and pc.launches[0].ntaps == 1 and x.shape[1] % 8 == 0
+    return _conv2d_mfma(x, pc, pc.launches[0], _epilogue(scale, shift, relu, residual), out, _tile_list(tile_list, n_list), tile_cfg)
 
 
-def _pair_args(x, pc_a, pc_b, weights, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a, residual_b):
-    """what the three launches of a transposed-conv pair begin with: the input, the two layers' `weights` (None: the four classes'
-    packings and the tap tables they share), the outputs and their epilogues"""
+def _pair_args(x, pc_a, pc_b, weights, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a, residual_b, tile_list, n_list):
+    """what the launches of a transposed-conv pair take but for their tile_cfg: the input, the two layers' `weights` (None: the four
+    classes' packings and the tap tables they share), the outputs, their epilogues and the tile list (None: the whole map)"""
     _req(x, torch.float32, "x")
     B, ci, H, W = x.shape
     assert pc_a.kind == pc_b.kind == "deconv" and pc_a.cin == pc_b.cin == ci and pc_a.cout == pc_b.cout
     if weights is None:
         weights = (_addr(pc_a.wpk4), _addr(pc_b.wpk4), pc_a.ntaps4.data_ptr(), pc_a.dy4.data_ptr(), pc_a.dx4.data_ptr())
-    return (x.data_ptr(), B, ci, H, W, *weights, out_a.data_ptr(), out_b.data_ptr(), pc_a.cout, _p(scale_a), _p(shift_a), _p(scale_b),
-            _p(shift_b), 1 if relu else 0, _p(residual_a), _p(residual_b))
+    return (x.data_ptr(), B, ci, H, W, *weights, out_a.data_ptr(), out_b.data_ptr(), pc_a.cout, _epilogue(scale_a, shift_a, relu, residual_a),
+            _epilogue(scale_b, shift_b, relu, residual_b), None if tile_list is None else _tile_list(tile_list, n_list))
+
+
+def deconv2d_s2_pair(x, pc_a, pc_b, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a=None, residual_b=None, tile_cfg=4):
+    """Two ConvTranspose2d(3, 2, 1, 1) layers of one shape on the SAME input in one launch (sessd_deconv2d_s2_mfma_pair); the same
+    bits as two conv2d() calls with that tile_cfg (3, 4, 11 or 12)."""
+    return deconv2d_s2_pair_active(x, pc_a, pc_b, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, None, None, residual_a, residual_b,
+                                   tile_cfg)
 
 
 def deconv2d_s2_pair_active(x, pc_a, pc_b, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, tile_list, n_list, residual_a=None,
                             residual_b=None, tile_cfg=11):
-    """sessd_deconv2d_s2_mfma_pair_active: deconv2d_s2_pair over the listed 2x2 tiles of the INPUT map only (a listed tile = a 4x4
-    block of both outputs); the other output pixels are left alone."""
-    _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
-    args = _pair_args(x, pc_a, pc_b, None, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a, residual_b)
-    check(lib.sessd_deconv2d_s2_mfma_pair_active(*args, tile_list.data_ptr(), n_list.data_ptr(), tile_list.numel(), int(tile_cfg),
-                                                 _stream()), "deconv2d_s2_mfma_pair_active")
+    """sessd_deconv2d_s2_mfma_pair with a tile list: deconv2d_s2_pair over the listed 2x2 tiles of the INPUT map only (a listed tile = a
+    4x4 block of both outputs); the other output pixels are left alone."""
+    args = _pair_args(x, pc_a, pc_b, None, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a, residual_b, tile_list, n_list)
+    check(lib.sessd_deconv2d_s2_mfma_pair(*args, int(tile_cfg), _stream()), "deconv2d_s2_mfma_pair")
     return out_a, out_b
 
 
@@ -2028,14 +2047,12 @@ def deconv2d_s2_pair_split_active(x, pc_a, pc_b, scale_a, shift_a, scale_b, shif
                                   residual_b=None):
     """sessd_deconv2d_s2_pair_split_active: deconv2d_s2_pair_active on the bf16 matrix cores (three-way split operands, f32
     accuracy) -- the listed 2x2 tiles of the INPUT map give 4x4 blocks of both outputs, the other output pixels are left alone."""
-    _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
     wa, wb = pc_a.wsplit(), pc_b.wsplit()
     if wa is None or wb is None:
         raise ValueError("deconv2d_s2_pair_split_active needs cin % 16 == 0")
     args = _pair_args(x, pc_a, pc_b, (wa.data_ptr(), wb.data_ptr()), scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a,
-                      residual_b)
-    check(lib.sessd_deconv2d_s2_pair_split_active(*args, tile_list.data_ptr(), n_list.data_ptr(), tile_list.numel(), _stream()),
-          "deconv2d_s2_pair_split_active")
+                      residual_b, tile_list, n_list)
+    check(lib.sessd_deconv2d_s2_pair_split_active(*args, _stream()), "deconv2d_s2_pair_split_active")
     return out_a, out_b
 
 
@@ -2065,7 +2082,8 @@ def conv2d_s2_split_active(x, pc, scale, shift, relu, out, tile_list, n_list, re
     """sessd_conv2d_s2_split_active: a Conv2d(3, stride 2, padding 1) layer on the bf16 matrix cores (three-way split operands, f32
     accuracy) over the listed 2x2 tiles of its OUTPUT map (entries image * (ho/2 * wo/2) + tile, count on the device); the other
     output pixels of `out` are left alone."""
-    _req(x, torch.float32, "x"); _req(out, torch.float32, "out"); _req(tile_list, torch.int32, "tile_list"); _req(n_list, torch.int32, "n_list")
+    _req(x, torch.float32, "x"); _req(out, torch.float32, "out")
+    tl = _tile_list(tile_list, n_list)
     ws = pc.wsplit_s2()
     if ws is None:
         raise ValueError("conv2d_s2_split_active needs a 3x3 stride-2 conv with cin % 16 == 0")
@@ -2073,9 +2091,8 @@ def conv2d_s2_split_active(x, pc, scale, shift, relu, out, tile_list, n_list, re
     ho, wo = pc.out_hw(H, W)
     if ci != pc.cin or tuple(out.shape) != (B, pc.cout, ho, wo):
         raise ValueError("conv2d_s2_split_active: x (B, cin, H, W) and out (B, cout, ceil(H/2), ceil(W/2))")
-    check(lib.sessd_conv2d_s2_split_active(x.data_ptr(), B, ci, H, W, ws.data_ptr(), out.data_ptr(), pc.cout, ho, wo, _p(scale), _p(shift),
-                                           1 if relu else 0, _p(residual), tile_list.data_ptr(), n_list.data_ptr(), tile_list.numel(),
-                                           _stream()), "conv2d_s2_split_active")
+    check(lib.sessd_conv2d_s2_split_active(x.data_ptr(), B, ci, H, W, ws.data_ptr(), out.data_ptr(), pc.cout, ho, wo,
+                                           _epilogue(scale, shift, relu, residual), tl, _stream()), "conv2d_s2_split_active")
     return out
 
 
@@ -2298,16 +2315,7 @@ def conv2d_train_covers(m, x, padded=False):
     return B * ci * H * W * 4 < 0x7FFFFFFF and B * co * Ho * Wo * 4 < 0x7FFFFFFF
 
 
-def deconv2d_s2_pair(x, pc_a, pc_b, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a=None, residual_b=None, tile_cfg=4):
-    """Two ConvTranspose2d(3, 2, 1, 1) layers of one shape on the SAME input in one launch (sessd_deconv2d_s2_mfma_pair); the same
-    bits as two conv2d() calls with that tile_cfg (3, 4, 11 or 12)."""
-    args = _pair_args(x, pc_a, pc_b, None, scale_a, shift_a, scale_b, shift_b, relu, out_a, out_b, residual_a, residual_b)
-    check(lib.sessd_deconv2d_s2_mfma_pair(*args, int(tile_cfg), _stream()), "deconv2d_s2_mfma_pair")
-    return out_a, out_b
-
-
-# conv2d's kernel families. Each takes the layer as conv2d does, with `out` allocated, and epi = (scale, shift, relu, residual) as
-# the C entries take them.
+# conv2d's kernel families. Each takes the layer as conv2d does, with `out` allocated, and epi = _epilogue(...).
 def _conv2d_winograd_sk(x, pc, epi, out, shape, workspace, workgroups):
     B, ci, H, W = x.shape
     upk = pc.upk_sk(shape)
@@ -2316,25 +2324,22 @@ def _conv2d_winograd_sk(x, pc, epi, out, shape, workspace, workgroups):
                          "and even H, W")
     need = int(lib.sessd_conv3x3_winograd_sk_workspace_bytes(B, H, W, pc.cout, shape, workgroups))
     workspace = _sk_workspace(workspace, need, shape, workgroups, x.device)
-    check(lib.sessd_conv3x3_winograd_sk(x.data_ptr(), B, ci, H, W, upk.data_ptr(), out.data_ptr(), pc.cout, *epi, workspace.data_ptr(),
-                                        workspace.numel(), shape, workgroups, _stream()), "conv3x3_winograd_sk")
+    _winograd_sk(x, 1, upk, out, pc.cout, epi, None, _stream_k(workspace, workgroups), shape)
 
 
-def _conv2d_sk(x, pc, epi, out, workspace, workgroups):
-    sk = pc.sk_args()
-    if sk is None:
+def _conv2d_sk_whole(x, pc, epi, out, workspace, workgroups):
+    if pc.sk_args() is None:
         raise ValueError("tile_cfg 30 (LDS-tiled stream-K) needs cin % 16 == 0")
-    need = int(lib.sessd_conv2d_sk_workspace_bytes(x.shape[0], *pc.tile_hw(*x.shape[2:]), pc.cout, sk["n"], workgroups))
+    need = int(lib.sessd_conv2d_sk_workspace_bytes(x.shape[0], *pc.tile_hw(*x.shape[2:]), pc.cout, pc.sk_args()["n"], workgroups))
     workspace = _sk_workspace(workspace, need, "csk", workgroups, x.device)
-    check(lib.sessd_conv2d_sk(*_sk_layer_args(x, pc, sk, epi, out), workspace.data_ptr(), workspace.numel(), workgroups, _stream()),
-          "conv2d_sk")
+    _conv2d_sk(x, pc, epi, out, None, _stream_k(workspace, workgroups), "tile_cfg 30")
 
 
 def _conv2d_winograd(x, pc, epi, out, variant):
     B, ci, H, W = x.shape
     if pc.upk is None or (H & 1) or (W & 1):
         raise ValueError("tile_cfg 20/21 (Winograd) needs a 3x3 stride-1 conv with cin % 8 == 0 and even H, W")
-    check(lib.sessd_conv3x3_winograd(x.data_ptr(), B, ci, H, W, pc.upk.data_ptr(), out.data_ptr(), pc.cout, *epi, variant, _stream()),
+    check(lib.sessd_conv3x3_winograd(x.data_ptr(), B, ci, H, W, pc.upk.data_ptr(), out.data_ptr(), pc.cout, epi, variant, _stream()),
           "conv3x3_winograd")
 
 
@@ -2342,16 +2347,13 @@ def _deconv2d_s2_merged(x, pc, epi, out, tile_cfg):
     B, ci, H, W = x.shape
     cfg = tile_cfg if tile_cfg is not None else default_tile_cfg(pc.cout, H * W, 4)
     check(lib.sessd_deconv2d_s2_mfma(x.data_ptr(), B, ci, H, W, _addr(pc.wpk4), pc.ntaps4.data_ptr(), pc.dy4.data_ptr(), pc.dx4.data_ptr(),
-                                     out.data_ptr(), pc.cout, *epi, cfg, _stream()), "deconv2d_s2_mfma")
+                                     out.data_ptr(), pc.cout, epi, cfg, _stream()), "deconv2d_s2_mfma")
 
 
 def _conv2d_direct(x, pc, epi, out, tile_cfg):
-    B, ci, H, W = x.shape
-    (Ho, Wo), (th, tw) = pc.out_hw(H, W), pc.tile_hw(H, W)
+    th, tw = pc.tile_hw(*x.shape[2:])
     for la in pc.launches:
-        cfg = tile_cfg if tile_cfg is not None else default_tile_cfg(pc.cout, th * tw, la.ntaps)
-        check(lib.sessd_conv2d_mfma(x.data_ptr(), B, ci, H, W, la.wpk.data_ptr(), la.ntaps, la.dy.data_ptr(), la.dx.data_ptr(), la.in_mul,
-                                    th, tw, out.data_ptr(), pc.cout, Ho, Wo, la.out_mul, la.py, la.px, *epi, cfg, _stream()), "conv2d_mfma")
+        _conv2d_mfma(x, pc, la, epi, out, None, tile_cfg if tile_cfg is not None else default_tile_cfg(pc.cout, th * tw, la.ntaps))
 
 
 def conv2d(x, pc, scale=None, shift=None, relu=True, residual=None, out=None, tile_cfg=None, workspace=None, workgroups=0):
@@ -2377,11 +2379,11 @@ def conv2d(x, pc, scale=None, shift=None, relu=True, residual=None, out=None, ti
         raise ValueError("a kernel-size = stride transposed conv runs on the sessd_conv2d_mfma tilings only")
     if out is None:
         out = torch.empty((B, pc.cout, *pc.out_hw(H, W)), dtype=torch.float32, device=x.device)
-    epi = (_p(scale), _p(shift), 1 if relu else 0, _p(residual))
+    epi = _epilogue(scale, shift, relu, residual)
     if tile_cfg in (22, 23, 24, 25):
         _conv2d_winograd_sk(x, pc, epi, out, tile_cfg - 22, workspace, workgroups)
     elif tile_cfg == 30:
-        _conv2d_sk(x, pc, epi, out, workspace, workgroups)
+        _conv2d_sk_whole(x, pc, epi, out, workspace, workgroups)
     elif tile_cfg in (20, 21):
         _conv2d_winograd(x, pc, epi, out, tile_cfg - 20)
     elif pc.kind == "deconv" and ci % 8 == 0:

@@ -41,39 +41,87 @@ def test_ops_refuse_cpu_tensors():
         ops.boxes_pairwise(1, torch.zeros(2, 5), torch.zeros(2, 5))
 
 
+def _struct_fields(name):
+    """(C type, is pointer, field name, array length or None) of every member of a typedef struct of sessd_hip_types.h"""
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sessd_hip_types.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct \{([^}]*)\} %s;" % name, txt).group(1)
+    decls = [re.fullmatch(r"(?:const\s+)?(\w+)\s*(\*?)\s*(\w+)(?:\[(\d+)\])?", d.strip()).groups() for d in body.split(";") if d.strip()]
+    return [(ctype, bool(star), field, int(dim) if dim else None) for ctype, star, field, dim in decls]
+
+
+def test_dense_argument_structs_mirror_the_header():
+    """sessd_conv_epilogue_t, sessd_tile_list_t and sessd_stream_k_t against their ctypes mirrors in _lib.py: the same fields in the
+    same order with the same C types, and the size a C compiler gives the struct as the header spells it."""
+    import ctypes
+    from sessd_hip import _lib
+    scalar = {"int32_t": ctypes.c_int32, "size_t": ctypes.c_size_t}
+    want = {"sessd_conv_epilogue_t": (_lib.ConvEpilogue, ["scale", "shift", "residual", "relu"]),
+            "sessd_tile_list_t": (_lib.TileList, ["tiles", "count", "cap"]),
+            "sessd_stream_k_t": (_lib.StreamK, ["workspace", "workspace_bytes", "workgroups", "min_rounds"])}
+    for cname, (mirror, names) in want.items():
+        parsed = _struct_fields(cname)
+        assert [f[2] for f in parsed] == names == [n for n, _ in mirror._fields_], cname
+        for (ctype, star, field, dim), (_, ptype) in zip(parsed, mirror._fields_):
+            assert dim is None and ptype is (ctypes.c_void_p if star else scalar[ctype]), (cname, field)
+        header = type("header_" + cname, (ctypes.Structure,),
+                      {"_fields_": [(f, ctypes.c_void_p if star else scalar[ctype]) for ctype, star, f, _ in parsed]})
+        assert ctypes.sizeof(mirror) == ctypes.sizeof(header), cname
+    assert ctypes.sizeof(_lib.ConvEpilogue) == 32 and ctypes.sizeof(_lib.TileList) == 24 and ctypes.sizeof(_lib.StreamK) == 24   # LP64
+
+
 def test_dense_entry_points_reject_bad_shapes_before_touching_the_device():
-    """Argument checks of the dense-conv entry points added in round 2 come before any device call: they can be exercised here
-    (null pointers, no GPU). SESSD_EINVAL = -1; workspace-size queries return 0 for bad arguments."""
+    """Argument checks of the dense-conv entry points come before any device call: they can be exercised here (null device
+    pointers, no GPU). SESSD_EINVAL = -1; workspace-size queries return 0 for bad arguments. A merged entry (NULL list = the whole
+    map) refuses what either of the two entries it replaces refused."""
+    import ctypes
     import sessd_hip
+    from sessd_hip._lib import ConvEpilogue, StreamK, TileList
     lib = sessd_hip.lib
-    # LDS-tiled stream-K conv: cin % 16, class count, workgroups % 8, 32-bit buffer offsets
-    sk = lambda cin, nclass, wgs, hw=16: lib.sessd_conv2d_sk(None, 1, cin, hw, hw, nclass, None, None, None, None, 1, hw, hw, None, 32, hw, hw, 1,
-                                                             None, None, None, None, 1, None, None, 0, wgs, None)
-    assert sk(24, 1, 8) == -1 and sk(32, 5, 8) == -1 and sk(32, 1, 12) == -1 and sk(4096, 1, 8, hw=1024) == -1
+    one = ctypes.c_int32(1)
+    ptr = ctypes.addressof(one)
+    epi = ConvEpilogue(relu=1)
+    wg8 = StreamK(workgroups=8)
+    ints = lambda *v: ctypes.cast((ctypes.c_int * len(v))(*v), ctypes.c_void_p)
+    # LDS-tiled stream-K conv: cin % 16, class count, workgroups % 8, 32-bit buffer offsets, no stream-K block
+    sk = lambda cin=32, nclass=1, wgs=8, hw=16, batch=1, tl=None, sk=True: lib.sessd_conv2d_sk(
+        None, batch, cin, hw, hw, nclass, None, None, None, None, 1, hw, hw, None, 32, hw, hw, 1, None, None, epi, tl,
+        StreamK(workgroups=wgs, min_rounds=1) if sk else None, None)
+    assert sk(cin=24) == -1 and sk(nclass=5) == -1 and sk(wgs=12) == -1 and sk(cin=4096, hw=1024) == -1 and sk(sk=False) == -1
     assert lib.sessd_conv2d_sk_workspace_bytes(0, 8, 8, 32, 1, 8) == 0 and lib.sessd_conv2d_sk_workspace_bytes(1, 8, 8, 32, 5, 8) == 0
     # explicit workgroup count: pure arithmetic (counters of nclass * batch * pixel tiles * cout groups + two 64 KB slots per workgroup)
     assert lib.sessd_conv2d_sk_workspace_bytes(2, 100, 88, 256, 1, 256) == 256 * ((2 * 69 * 2 * 4 + 255) // 256) + 2 * 256 * 65536
     assert lib.sessd_conv2d_sk_pack(None, 1, 1, None, 1, 32, 24, None, None) == -1
     # its active-tile mode: a tile list with its device count, even tile space, the WHOLE batch inside 32-bit offsets
-    import ctypes
-    one = ctypes.c_int32(1)
-    ska = lambda tl, nl, cap, hw=16, batch=1, cin=32: lib.sessd_conv2d_sk_active(None, batch, cin, hw, hw, 1, None, None, None, None, 1, hw, hw, None, 32,
-                                                                                 hw, hw, 1, None, None, None, None, 1, None, tl, nl, cap, 1, None, 0, 8, None)
-    ptr = ctypes.addressof(one)
-    assert ska(None, ptr, 4) == -1 and ska(ptr, None, 4) == -1 and ska(ptr, ptr, 0) == -1 and ska(ptr, ptr, 4, hw=15) == -1
-    assert ska(ptr, ptr, 4, hw=1024, batch=32, cin=16) == -1
+    assert sk(tl=TileList(None, ptr, 4)) == -1 and sk(tl=TileList(ptr, None, 4)) == -1 and sk(tl=TileList(ptr, ptr, 0)) == -1
+    assert sk(tl=TileList(ptr, ptr, 4), hw=15) == -1
+    assert sk(tl=TileList(ptr, ptr, 4), hw=1024, batch=32, cin=16) == -1
     # tile activity: a stride-2 step that takes a slot needs an output of even size; at most eight slots; step 4 only behind a step 3
     steps = lambda *v: (ctypes.c_int32 * len(v))(*v)
     act = lambda st, h=200, w=176: lib.sessd_bev_tile_activity(ptr, ptr, 1, 1, h, w, st, len(st), ptr, ptr, ptr, 1, None, 0, None)
     assert act(steps(2), h=202) == -1 and act(steps(0, 0, 0, 2, 0, 0, 0, 0, 0)) == -1 and act(steps(4)) == -1 and act(steps(0, 4)) == -1 and act(steps(3), w=192) == -1
     assert act(steps(3, 4, 0), h=200, w=100) == -1   # the doubled map must fit the kernel's pixel rows
     assert lib.sessd_fill_inactive_tiles(None, 13, 1, None) == -1
-    # Winograd stream-K over weight sets: the batch must split evenly
-    assert lib.sessd_conv3x3_winograd_sk_sets(None, 3, 2, 128, 8, 8, None, None, 128, None, None, 1, None, None, 0, 0, 8, None) == -1
-    assert lib.sessd_conv3x3_winograd_sk_sets(None, 2, 2, 128, 7, 8, None, None, 128, None, None, 1, None, None, 0, 0, 8, None) == -1
-    # two transposed convs in one launch / fused SSFA tail + heads
-    assert lib.sessd_deconv2d_s2_mfma_pair(None, 1, 12, 8, 8, None, None, None, None, None, None, None, 32, None, None, None, None, 1, None, None,
-                                           4, None) == -1
+    # Winograd stream-K over weight sets: the batch must split evenly, even maps; with a list: one set, not shape 2, a whole list
+    wsk = lambda batch=2, nsets=1, h=8, w=8, tl=None, shape=0, sk=wg8: lib.sessd_conv3x3_winograd_sk(
+        None, batch, nsets, 128, h, w, None, None, 128, epi, tl, sk, shape, None)
+    lst = TileList(ptr, ptr, 4)
+    assert wsk(batch=3, nsets=2) == -1 and wsk(nsets=2, h=7) == -1 and wsk(sk=None) == -1 and wsk(sk=StreamK(workgroups=12)) == -1
+    assert wsk(nsets=2, tl=lst) == -1 and wsk(tl=lst, shape=2) == -1
+    assert wsk(tl=TileList(None, ptr, 4)) == -1 and wsk(tl=TileList(ptr, None, 4)) == -1 and wsk(tl=TileList(ptr, ptr, 0)) == -1
+    assert wsk() == -2 and wsk(nsets=2) == -2 and wsk(tl=lst) == -2 and wsk(shape=2) == -2   # past every check: no workspace given
+    # the direct kernel over a tile list: four effective taps, tile_cfg 3 / 4 / 11 / 12, even tile space, the whole batch in 32 bits
+    z9 = ints(*([0] * 9))
+    mf = lambda ntaps=1, cfg=11, hw=16, batch=1, cin=32, tl=lst: lib.sessd_conv2d_mfma(
+        None, batch, cin, hw, hw, None, ntaps, z9, z9, 1, hw, hw, None, 32, hw, hw, 1, 0, 0, epi, tl, cfg, None)
+    assert mf(cfg=1) == -1 and mf(ntaps=9) == -1 and mf(cin=36) == -1 and mf(hw=15) == -1 and mf(cfg=13) == -1
+    assert mf(hw=1024, batch=32, cin=16) == -1
+    assert mf(tl=TileList(None, ptr, 4)) == -1 and mf(tl=TileList(ptr, None, 4)) == -1 and mf(tl=TileList(ptr, ptr, 0)) == -1
+    assert mf(cin=31, tl=None) == -1 and mf(ntaps=10, tl=None) == -1 and mf(cfg=9, tl=None) == -1   # the whole-map launch's own
+    # two transposed convs in one launch: cin % 8; with a list also even hin / win
+    pair = lambda cin=16, hin=8, tl=None: lib.sessd_deconv2d_s2_mfma_pair(None, 1, cin, hin, 8, None, None, None, None, None, None, None, 32,
+                                                                        epi, epi, tl, 4, None)
+    assert pair(cin=12) == -1 and pair(hin=7, tl=lst) == -1 and pair(tl=TileList(ptr, ptr, 0)) == -1
+    # fused SSFA tail + heads
     assert lib.sessd_ssfa_fuse_head(None, None, None, None, 1.0, 0.0, 1.0, 0.0, 1, 100, 64, None, None, None, 22, None, None) == -1
     assert lib.sessd_ssfa_fuse_head(None, None, None, None, 1.0, 0.0, 1.0, 0.0, 1, 128, 64, None, None, None, 21, None, None) == -1
 
@@ -187,12 +235,10 @@ def test_predict_args_mirror_and_argument_checks():
     from sessd_hip._lib import DiCfg, PredictArgs
     lib = sessd_hip.lib
     assert ctypes.sizeof(PredictArgs) == lib.sessd_predict_args_bytes()
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sessd_hip_types.h")).read(), flags=re.S)
-    body = re.search(r"typedef struct \{([^}]*)\} sessd_predict_args_t;", txt).group(1)
-    decls = [re.fullmatch(r"(const\s+)?(\w+)\s*(\*?)\s*(\w+)(\[(\d+)\])?", d.strip()).groups() for d in body.split(";") if d.strip()]
+    decls = _struct_fields("sessd_predict_args_t")
     scalar = dict(int32_t=ctypes.c_int, float=ctypes.c_float)
     assert len(decls) == len(PredictArgs._fields_) == 29
-    for (_, ctype, star, name, _, dim), (pname, ptype) in zip(decls, PredictArgs._fields_):
+    for (ctype, star, name, dim), (pname, ptype) in zip(decls, PredictArgs._fields_):
         assert name == pname
         if star:
             assert ptype is ctypes.c_void_p or (ctype == "sessd_di_cfg_t" and ptype is ctypes.POINTER(DiCfg)), name

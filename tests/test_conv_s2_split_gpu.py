@@ -153,11 +153,12 @@ def test_bad_arguments_return_the_error_code(dev):
     x, pc = d["x"].to(dev), ops.pack_conv2d(d["w"].to(dev), stride=2)
     tl, nl = torch.zeros(4, dtype=torch.int32, device=dev), torch.ones(1, dtype=torch.int32, device=dev)
     out = torch.full((B, cout, 4, 4), float("nan"), device=dev)
+    epi, lst = ops._epilogue(None, None, True, None), ops._tile_list(tl, nl)
     rc = ops.lib.sessd_conv2d_s2_split_active(x.data_ptr(), B, cin, hin, win, pc.wsplit_s2().data_ptr(), out.data_ptr(), cout, 4, 6,
-                                              None, None, 1, None, tl.data_ptr(), nl.data_ptr(), 4, None)
+                                              epi, lst, None)
     assert rc == -1
     rc = ops.lib.sessd_conv2d_s2_split_active(x.data_ptr(), B, 24, hin, win, pc.wsplit_s2().data_ptr(), out.data_ptr(), cout, 4, 4,
-                                              None, None, 1, None, tl.data_ptr(), nl.data_ptr(), 4, None)
+                                              epi, lst, None)
     assert rc == -1
     with pytest.raises(ValueError):
         ops.conv2d_s2_split_active(x, ops.pack_conv2d(d["w"].to(dev), stride=1), None, None, True, out, tl, nl)

@@ -64,8 +64,11 @@ def test_entry_point_rejects_bad_arguments_before_touching_the_device():
     import sessd_hip
     one = ctypes.c_int32(1)
     p = ctypes.addressof(one)
+    from sessd_hip._lib import ConvEpilogue, TileList
     f = lambda cin=32, hin=8, win=8, batch=1, cout=32, hout=4, wout=4, tl=p, nl=p, cap=4, w=p, x=p, out=p: \
-        sessd_hip.lib.sessd_conv2d_s2_split_active(x, batch, cin, hin, win, w, out, cout, hout, wout, None, None, 1, None, tl, nl, cap, None)
+        sessd_hip.lib.sessd_conv2d_s2_split_active(x, batch, cin, hin, win, w, out, cout, hout, wout, ConvEpilogue(relu=1),
+                                                   TileList(tl, nl, cap), None)
+    assert sessd_hip.lib.sessd_conv2d_s2_split_active(p, 1, 32, 8, 8, p, p, 32, 4, 4, None, None, None) == -1    # no list at all
     assert f(cin=24) == -1 and f(cin=0) == -1 and f(batch=0) == -1 and f(cout=0) == -1
     assert f(hout=3, hin=6) == -1 and f(wout=5, win=10) == -1            # odd output maps have no 2x2 tile grid
     assert f(hin=9) == -1 and f(hin=6) == -1 and f(win=9) == -1 and f(win=6) == -1   # hin in {2 hout - 1, 2 hout}

@@ -47,8 +47,11 @@ def test_entry_point_rejects_bad_arguments_before_touching_the_device():
     import sessd_hip
     one = ctypes.c_int32(1)
     p = ctypes.addressof(one)
-    f = lambda cin=32, hin=8, win=8, batch=1, cout=32, tl=p, nl=p, cap=4, wa=p: sessd_hip.lib.sessd_deconv2d_s2_pair_split_active(
-        p, batch, cin, hin, win, wa, p, p, p, cout, None, None, None, None, 1, None, None, tl, nl, cap, None)
+    from sessd_hip._lib import ConvEpilogue, TileList
+    f = lambda cin=32, hin=8, win=8, batch=1, cout=32, tl=p, nl=p, cap=4, wa=p, relu_b=1: sessd_hip.lib.sessd_deconv2d_s2_pair_split_active(
+        p, batch, cin, hin, win, wa, p, p, p, cout, ConvEpilogue(relu=1), ConvEpilogue(relu=relu_b), TileList(tl, nl, cap), None)
+    assert sessd_hip.lib.sessd_deconv2d_s2_pair_split_active(p, 1, 32, 8, 8, p, p, p, p, 32, None, None, None, None) == -1   # no list at all
+    assert f(relu_b=0) == -1   # the kernel has one activation for both layers
     assert f(cin=24) == -1 and f(cin=0) == -1 and f(hin=7) == -1 and f(win=9) == -1 and f(batch=0) == -1 and f(cout=0) == -1
     assert f(tl=None) == -1 and f(nl=None) == -1 and f(cap=0) == -1 and f(wa=None) == -1
     assert f(cin=16, hin=1024, win=1024, batch=32) == -1 and f(cin=4096, hin=1024, win=1024, cout=1) == -1   # 32-bit buffer offsets

@@ -270,7 +270,7 @@ def test_active_chain_through_the_stride_2_layer(dev):
 
 @pytest.mark.parametrize("batch,min_rounds", [(1, 1), (1, 4), (2, 2), (3, 8)])
 def test_stride_2_and_1x1_layers_over_tile_lists(dev, batch, min_rounds):
-    """rpn_v1.py:150-152,163-172 in active-tile mode (conv2d_sk_kernel<LIST>, sessd_conv2d_sk_active): the stride-2 conv that opens
+    """rpn_v1.py:150-152,163-172 in active-tile mode (conv2d_sk_kernel<LIST>, sessd_conv2d_sk with a tile list): the stride-2 conv that opens
     block 1 over ITS tile list (step 2 of the activity program), the 1x1 trans layers over the list of the layer that produced
     their input -- against the dense stream-K launches on the same inputs. A computed pixel is the dense kernel's arithmetic in
     another summation split (stream-K shares differ): 1e-5 of the layer's largest value; filled pixels: the constants' chain."""
@@ -347,8 +347,8 @@ def test_stride_2_and_1x1_layers_over_tile_lists(dev, batch, min_rounds):
 
 @pytest.mark.parametrize("batch,cfg", [(1, 11), (2, 4), (3, 12), (1, 3)])
 def test_direct_kernels_over_tile_lists(dev, batch, cfg):
-    """rpn_v1.py:163-199, 224 on the direct kernel over lists (conv_body<.., LIST>: sessd_conv2d_mfma_active,
-    sessd_deconv2d_s2_mfma_pair_active): trans_0 over the list of the layer that produced its input, the two transposed convs
+    """rpn_v1.py:163-199, 224 on the direct kernel over lists (conv_body<.., LIST>: sessd_conv2d_mfma and
+    sessd_deconv2d_s2_mfma_pair with a tile list): trans_0 over the list of the layer that produced its input, the two transposed convs
     over the step-3 slot (2x2 tiles of their input = 4x4 output blocks; residual from the full-resolution layer). A computed pixel
     is the plain launch's code: BIT-EQUAL to it on the same input; a filled pixel: the constants' chain (one value per output
     parity class for the transposed convs), 1e-5 of the layer's largest value."""

@@ -118,7 +118,7 @@ def test_winograd_stream_k(dev, cin, cout, H, W, B, wgs, cfg):
 @pytest.mark.parametrize("shape,B,H,W,wgs", [(0, 1, 200, 176, 0), (1, 2, 24, 40, 0), (0, 2, 10, 66, 8), (1, 1, 14, 18, 16), (2, 1, 200, 176, 0),
                                              (2, 2, 10, 66, 8)])
 def test_winograd_stream_k_weight_sets(dev, shape, B, H, W, wgs):
-    """sessd_conv3x3_winograd_sk_sets: two layers of one shape (conv_0 / conv_1 of the SSFA neck) as ONE stream-K launch over a
+    """sessd_conv3x3_winograd_sk with nsets = 2: two layers of one shape (conv_0 / conv_1 of the SSFA neck) as ONE stream-K launch over a
     (2 B, C, H, W) input, each half with its own weights and BatchNorm constants, against the two single-layer launches."""
     C = 128
     g = torch.Generator().manual_seed(shape + H)

@@ -551,7 +551,7 @@ int sessd_nchw_channel_sum(const float* x, int batch, int channels, int plane, f
 /* ---- dense conv backward (training step): data gradients are launches of the forward entry points
  * above with re-packed weights (3x3 s1 <-> flipped 3x3 s1, 3x3 s2 <-> sessd_deconv2d_s2_mfma, 1x1 <-> 1x1); the weight
  * gradient of Conv2d(cin, cout, k, stride, padding k/2) is this pixel-reduction GEMM (deterministic: <= 64 row chunks
- * summed in order). k in {1,3}, stride in {1,2}, wout % 8 == 0. For ConvTranspose2d(3, s2, p1, op1) swap the roles
+ * summed in order). k in {1,3}, stride in {1,2}, wout % 8 == 0 (any wout: sessd_conv2d_wgrad_any_width). For ConvTranspose2d(3, s2, p1, op1) swap the roles
  * (input := its grad_out, grad_out := its input): the result is its (Cin, Cout, 3, 3) weight gradient.
  * Replaces the ATen/MIOpen backward of det3d/models/necks/rpn_v1.py:135-235 under trainer_sessd.py:250-275. */
 /* Every dense weight packing of a training iteration (sessd_conv2d_pack_taps / sessd_conv3x3_winograd_pack jobs) in ONE launch. */
@@ -560,6 +560,16 @@ size_t sessd_conv2d_wgrad_workspace_bytes(int cout, int cin, int ksize);
 int sessd_conv2d_wgrad(const float* input, int batch, int cin, int hin, int win, const float* grad_out, int cout, int hout,
                        int wout, int ksize, int stride, float* grad_weight, void* workspace, size_t workspace_bytes,
                        sessd_stream_t stream);
+/* The same weight gradient at ANY wout >= 1: the argument list, the workspace query (sessd_conv2d_wgrad_workspace_bytes) and
+ * every other refusal of sessd_conv2d_wgrad (k, stride, win == 2 * wout at stride 2, 2 GiB per tensor, SESSD_EWORKSPACE). For
+ * wout % 8 == 0 it issues exactly the launches of sessd_conv2d_wgrad (the same bits). Any other width runs the same three
+ * kernels with ragged rows: a step that ends past the row keeps only its in-row pixels, and no load is wider than the row
+ * alignment allows (wout % 4 == 0: 16-byte loads; even: 8-byte loads of grad_out; odd: dword loads of grad_out; the input of
+ * a stride-2 layer, twice as wide, is one class up). Same chunk rule, same ordered sum: deterministic, no float atomics.
+ * sessd_conv2d_wgrad itself keeps refusing wout % 8 != 0. */
+int sessd_conv2d_wgrad_any_width(const float* input, int batch, int cin, int hin, int win, const float* grad_out, int cout,
+                                 int hout, int wout, int ksize, int stride, float* grad_weight, void* workspace,
+                                 size_t workspace_bytes, sessd_stream_t stream);
 
 /* The same weight gradient for Conv2d(cin, cout, 3, stride 1, padding 1) computed in the Winograd F(2x2,3x3) domain
  * (dU_xi = sum over 2x2 output tiles of (A dY A^T)_xi (B^T d B)_xi on the f32 matrix cores, then G^T dU G: 16 instead of 36

@@ -5,7 +5,9 @@ reported:
       64 -> 128 s = 1 at 248 x 216, 128 -> 128 s = 2 at 124 x 108, 256 -> 128 s = 4 at 62 x 54;
       ops.DeconvKsFunction against F.conv_transpose2d autograd on the same device;
   (b) one forward + backward of the whole train-mode neck, batch 2, for the PointPillars neck (64 x 496 x 432 canvas) and the
-      three-class config's neck (128 x 200 x 176): fused_train True against False (every layer its torch module).
+      three-class config's neck (128 x 200 x 176): fused_train True against False (every layer its torch module); for the
+      PointPillars neck a third arm, fused_train with train_any_width = True (the convs whose width is no multiple of 8 -- maps
+      124 x 108 and 62 x 54 -- on the device too, weight gradient by sessd_conv2d_wgrad_any_width).
 Writes profiles/rpn_train.json (or the path given) and prints the same JSON line.
 Usage: python scripts/rpn_train_probe.py [rounds] [out.json]"""
 import json
@@ -90,8 +92,8 @@ for name, (args, shape) in NECKS.items():
     with torch.no_grad():
         g = torch.randn_like(neck(x))
 
-    def step(fused, neck=neck, x=x, g=g):
-        neck.fused_train = fused
+    def step(fused, any_width=False, neck=neck, x=x, g=g):
+        neck.fused_train, neck.train_any_width = fused, any_width
         x.grad = None
         for p in neck.parameters():
             p.grad = None
@@ -101,11 +103,25 @@ for name, (args, shape) in NECKS.items():
     fused_grads = {k: p.grad.clone() for k, p in neck.named_parameters()}
     step(False)
     rel = max(float((fused_grads[k] - p.grad).abs().max() / p.grad.abs().max().clamp_min(1e-30)) for k, p in neck.named_parameters())
-    t = measure(dict(fused=(lambda: step(True), 10), torch=(lambda: step(False), 10)))
-    spread = max(t["fused"]["max"] - t["fused"]["min"], t["torch"]["max"] - t["torch"]["min"])
+    legs = dict(fused=(lambda: step(True), 10), torch=(lambda: step(False), 10))
+    third = name == "pointpillars"   # the only neck here with maps whose width is no multiple of 8
+    if third:
+        torch_grads = {k: p.grad.clone() for k, p in neck.named_parameters()}
+        step(True, True)
+        rel_any = max(float((torch_grads[k] - p.grad).abs().max() / torch_grads[k].abs().max().clamp_min(1e-30))
+                      for k, p in neck.named_parameters())
+        legs["any_width"] = (lambda: step(True, True), 10)
+    t = measure(legs)
+    spread = max(v["max"] - v["min"] for v in t.values())
     necks[name] = dict(input=list(shape), worst_rel_diff_param_grads_vs_torch=rel, fused_us=t["fused"], torch_us=t["torch"],
                        speedup=t["torch"]["median"] / t["fused"]["median"], rounds_spread_us=spread,
                        fused_slower_beyond_spread=bool(t["fused"]["median"] - t["torch"]["median"] > spread))
+    if third:
+        best_other = min(t["fused"]["median"], t["torch"]["median"])
+        necks[name].update(any_width_us=t["any_width"], any_width_worst_rel_diff_param_grads_vs_torch=rel_any,
+                           any_width_speedup_vs_torch=t["torch"]["median"] / t["any_width"]["median"],
+                           any_width_speedup_vs_fused=t["fused"]["median"] / t["any_width"]["median"],
+                           any_width_faster_than_both_beyond_spread=bool(best_other - t["any_width"]["median"] > spread))
     del neck, x, g, fused_grads
     torch.cuda.empty_cache()
 out["neck_forward_backward"] = necks

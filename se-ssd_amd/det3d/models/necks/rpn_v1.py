@@ -217,25 +217,27 @@ class RPN(nn.Module):
         self._low = _Lowered()
 
     fused_train = True   # train mode on the device: the layers the HIP kernels cover run on them (False: every torch module)
+    train_any_width = False   # True: convs of any output width on the device (sessd_conv2d_wgrad_any_width), not only wout % 8 == 0
 
     def _train_block(self, seq, x):
         """One block / deblock in train mode (batch-statistics BatchNorm, autograd), layer by layer: a conv that
         ops.conv2d_train_covers (with the ZeroPad2d(1) in front of it, which is its padding) on ops.Conv2dFunction, a transposed conv
         that ops.deconv_ks_covers on ops.DeconvKsFunction, a plain train-mode BatchNorm2d with the ReLU behind it on
         ops.bn2d_relu_train; anything else -- a layer the predicates refuse, a stride < 1 "up-sampler" Conv2d, another norm layer,
-        every layer of a CPU tensor or with fused_train = False -- runs its own torch module."""
+        every layer of a CPU tensor or with fused_train = False -- runs its own torch module. train_any_width = True lifts the
+        wout % 8 == 0 condition of the conv predicate (the weight gradient then goes through sessd_conv2d_wgrad_any_width)."""
         mods = list(seq._modules.values())
-        fused = self.fused_train and x.is_cuda
+        fused, anyw = self.fused_train and x.is_cuda, bool(self.train_any_width)
         i = 0
         while i < len(mods):
             m = mods[i]
             nxt = mods[i + 1] if i + 1 < len(mods) else None
             if (fused and isinstance(m, nn.ZeroPad2d) and tuple(m.padding) == (1, 1, 1, 1)
-                    and ops.conv2d_train_covers(nxt, x, padded=True)):
-                x = ops.conv2d_module(x, nxt)
+                    and ops.conv2d_train_covers(nxt, x, padded=True, any_width=anyw)):
+                x = ops.conv2d_module(x, nxt, any_width=anyw)
                 i += 2
-            elif fused and ops.conv2d_train_covers(m, x):
-                x = ops.conv2d_module(x, m)
+            elif fused and ops.conv2d_train_covers(m, x, any_width=anyw):
+                x = ops.conv2d_module(x, m, any_width=anyw)
                 i += 1
             elif fused and ops.deconv_ks_covers(m, x):
                 x = ops.DeconvKsFunction.apply(x, m.weight, int(m.stride[0]))

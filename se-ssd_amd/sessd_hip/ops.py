@@ -2277,7 +2277,7 @@ def deconv_ks_covers(m, x):
             and x.shape[1] == m.in_channels and _device_param(m.weight))
 
 
-def conv2d_train_covers(m, x, padded=False):
+def conv2d_train_covers(m, x, padded=False, any_width=False):
     """True only where ops.conv2d_module(x, m) runs forward AND backward on the HIP kernels (Conv2dFunction has no such check of its
     own: outside this domain it raises, or asserts, somewhere on the way). m: an nn.Conv2d with k in {1, 3} and stride in {1, 2}
     (k = 1: stride 1) on both axes, padding k // 2 -- or, with padded=True, the unpadded 3x3 conv behind an nn.ZeroPad2d(1), which is
@@ -2288,6 +2288,8 @@ def conv2d_train_covers(m, x, padded=False):
       stride 2: even H and W -- the data gradient is the ConvTranspose2d(3, 2, 1, 1) of pack_deconv2d_s2, whose output is twice
         its input, and sessd_conv2d_wgrad asks for win == 2 * wout;
       sessd_conv2d_wgrad: wout % 8 == 0, and the whole input and grad_out below 2 GiB (out_fits of sessd_conv2d_mfma asks less).
+    any_width=True asks for conv2d_module(x, m, any_width=True), whose weight gradient is sessd_conv2d_wgrad_any_width: the
+    wout % 8 condition falls away, every other one stays.
     A bias is covered: its gradient (ops.channel_sum) falls back by itself."""
     if not isinstance(m, torch.nn.Conv2d) or isinstance(m, torch.nn.ConvTranspose2d) or not _device_f32(x):
         return False
@@ -2310,7 +2312,7 @@ def conv2d_train_covers(m, x, padded=False):
     if s == 2 and (H % 2 or W % 2):
         return False
     Ho, Wo = (H + s - 1) // s, (W + s - 1) // s
-    if Wo % 8:
+    if Wo % 8 and not any_width:
         return False
     return B * ci * H * W * 4 < 0x7FFFFFFF and B * co * Ho * Wo * 4 < 0x7FFFFFFF
 
@@ -2600,11 +2602,13 @@ def mean_all(x):
 USE_WINOGRAD_WGRAD = os.environ.get("SESSD_WINOGRAD_WGRAD", "1") != "0"   # 3x3 stride-1 weight gradients in the Winograd domain
 
 
-def conv2d_wgrad(inp, grad_out, ksize, stride, winograd=None):
+def conv2d_wgrad(inp, grad_out, ksize, stride, winograd=None, any_width=False):
     """Weight gradient (Cout, Cin, k, k) of Conv2d(k, stride, padding k//2): inp (B,Cin,H,W), grad_out (B,Cout,Ho,Wo).
     For ConvTranspose2d(3, s2, p1, op1) pass (inp=its grad_out, grad_out=its input) and get its (Cin, Cout, 3, 3) gradient.
     winograd: None = the Winograd-domain kernel where it covers the layer and the map is large enough to fill the chip
-    (USE_WINOGRAD / USE_WINOGRAD_WGRAD), True = that kernel (ValueError outside its shapes), False = the direct kernel."""
+    (USE_WINOGRAD / USE_WINOGRAD_WGRAD), True = that kernel (ValueError outside its shapes), False = the direct kernel.
+    any_width: the direct kernel through sessd_conv2d_wgrad_any_width, which takes any Wo >= 1 (Wo % 8 == 0: the same launches and
+    bits); False keeps sessd_conv2d_wgrad and its refusal of Wo % 8 != 0. The Winograd choice does not look at it."""
     _req(inp, torch.float32, "inp")
     _req(grad_out, torch.float32, "grad_out")
     B, ci, hi, wi = inp.shape
@@ -2624,8 +2628,9 @@ def conv2d_wgrad(inp, grad_out, ksize, stride, winograd=None):
                                                    ws.numel(), _stream()), "conv3x3_wgrad_winograd")
             return gw
     ws = torch.empty(int(lib.sessd_conv2d_wgrad_workspace_bytes(co, ci, ksize)), dtype=torch.uint8, device=inp.device)
-    check(lib.sessd_conv2d_wgrad(inp.data_ptr(), B, ci, hi, wi, grad_out.data_ptr(), co, ho, wo, ksize, stride, gw.data_ptr(),
-                                 ws.data_ptr(), ws.numel(), _stream()), "conv2d_wgrad")
+    entry = lib.sessd_conv2d_wgrad_any_width if any_width else lib.sessd_conv2d_wgrad
+    check(entry(inp.data_ptr(), B, ci, hi, wi, grad_out.data_ptr(), co, ho, wo, ksize, stride, gw.data_ptr(), ws.data_ptr(), ws.numel(),
+                _stream()), "conv2d_wgrad_any_width" if any_width else "conv2d_wgrad")
     return gw
 
 
@@ -2651,6 +2656,10 @@ class Conv2dFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad):
+        return Conv2dFunction._backward(ctx, grad, False)
+
+    @staticmethod
+    def _backward(ctx, grad, any_width):
         x, weight = ctx.saved_tensors
         transposed, stride, has_bias = ctx.cfg
         g = grad.float().contiguous()
@@ -2666,16 +2675,27 @@ class Conv2dFunction(torch.autograd.Function):
                 pcd = packed_conv2d(w, 1, adjoint=True)
                 gx = conv2d(g, pcd, None, None, False, tile_cfg=_train_cfg(pcd, g))
         if ctx.needs_input_grad[1]:
-            gw = conv2d_wgrad(g, x, 3, 2) if transposed else conv2d_wgrad(x, g, k, stride)
+            gw = conv2d_wgrad(g, x, 3, 2, any_width=any_width) if transposed else conv2d_wgrad(x, g, k, stride, any_width=any_width)
         if has_bias and ctx.needs_input_grad[2]:
             gb = channel_sum(g)
         return gx, gw, gb, None, None
 
 
-def conv2d_module(x, m):
-    """Apply an nn.Conv2d / nn.ConvTranspose2d of the SSFA neck through Conv2dFunction (autograd-capable HIP path)."""
+class Conv2dFunctionAnyWidth(Conv2dFunction):
+    """Conv2dFunction with the weight gradient of sessd_conv2d_wgrad_any_width: maps of any width (conv2d_train_covers(...,
+    any_width=True)). A class of its own, so that Conv2dFunction's arguments and its autograd node's name stay what they are."""
+
+    @staticmethod
+    def backward(ctx, grad):
+        return Conv2dFunction._backward(ctx, grad, True)
+
+
+def conv2d_module(x, m, any_width=False):
+    """Apply an nn.Conv2d / nn.ConvTranspose2d of the SSFA neck through Conv2dFunction (autograd-capable HIP path);
+    any_width=True: through Conv2dFunctionAnyWidth."""
     transposed = isinstance(m, torch.nn.ConvTranspose2d)
-    return Conv2dFunction.apply(x, m.weight, m.bias, transposed, int(m.stride[0]))
+    fn = Conv2dFunctionAnyWidth if any_width else Conv2dFunction
+    return fn.apply(x, m.weight, m.bias, transposed, int(m.stride[0]))
 
 
 def default_tile_cfg(cout, npix, ntaps):

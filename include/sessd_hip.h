@@ -610,6 +610,28 @@ int sessd_head_loss(const sessd_head_loss_cfg_t* cfg, const sessd_head_loss_net_
                     float* grad_cls, float* grad_dir, float* grad_iou, float* record, void* workspace, size_t workspace_bytes,
                     sessd_stream_t stream);
 
+/* ---- The plain supervised multi-task head loss (the reference's three-class SECOND and PointPillars configs): values AND the
+ * gradient with respect to every task's box / cls / dir head outputs, all tasks in the same three launches (positives per
+ * block; per-anchor terms + gradients + block partials; ordered final sums) -- replaces, per task,
+ * det3d/models/bbox_heads/mg_head.py:559-652 (MultiGroupHead.loss) with create_loss (:155-193), prepare_loss_weights
+ * NormByNumPositives (:535-538), get_direction_target (:57-71), _get_pos_neg_loss (:42-54), the loss classes of
+ * det3d/models/losses/losses.py:146-203,364-418,489-531, and the trainer's sum over the tasks' `loss` entries.
+ * Per task: loss = loc_loss_weight * sum(smooth-L1 on the sin-encoded yaw) / B + cls_loss_weight * sum(sigmoid focal) / B +
+ * dir_loss_weight * sum(direction softmax on the positives) / B; classification and regression weights are divided by
+ * max(positives of the sample, 1); one class per task; code weights are ignored as the reference ignores them.
+ * tasks: HOST array of cfg->num_tasks entries. tasks[t].grad_* are WRITTEN in every element: d(sum over tasks of loss) /
+ * d(head output). record: (num_tasks + 1) x 32 device floats, every one written -- row t:
+ *   [0] loss, [1] cls_loss_reduced, [2] loc_loss_reduced, [3] dir_loss_reduced (UNWEIGHTED, as mg_head.py:625,636 logs it),
+ *   [4] cls_pos_loss, [5] cls_neg_loss, [6..12] loc_loss_elem, [13] num_pos, [14] num_neg (sample 0), [15] positives of the batch;
+ * row num_tasks: [0] the sum of the tasks' loss.
+ * _workspace_bytes returns 0 and the entry SESSD_EINVAL before any device call for batch < 1 (or > 1024), num_anchors < 1,
+ * batch * num_anchors >= 2^31, num_tasks outside 1..4, a sigma or class weight <= 0, null pointers; SESSD_EWORKSPACE for a
+ * workspace that is too small. Deterministic (block partials in double, summed in index order, no float atomics); static
+ * buffers and no host synchronisation: capturable in a hipGraph. */
+size_t sessd_supervised_loss_workspace_bytes(const sessd_supervised_loss_cfg_t* cfg);
+int sessd_supervised_loss(const sessd_supervised_loss_cfg_t* cfg, const sessd_supervised_task_t* tasks, float* record,
+                          void* workspace, size_t workspace_bytes, sessd_stream_t stream);
+
 /* ---- anchor target assignment: det3d/datasets/pipelines/preprocess.py:236-358 (AssignTarget) ->
  * det3d/core/anchor/target_assigner.py:68-136 -> det3d/core/anchor/target_ops_v3.py:11-137 (create_target_np) with the
  * nearest-IoU similarity (region_similarity.py:85-98) and second_box_encode (box_np_ops.py:52-110). anchors (n,7), gt_boxes

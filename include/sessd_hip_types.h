@@ -123,6 +123,29 @@ typedef struct {
   float center_range[6];                            /* post_center_range (mg_head_sessd.py:484) */
 } sessd_head_loss_cfg_t;
 
+/* ONE task of sessd_supervised_loss: the task's head outputs viewed as (B, A, 7) / (B, A) / (B, A, 2), its targets, and the
+ * gradient buffers of the same shapes, which the call WRITES in every element. All device pointers; dir / grad_dir 8-byte
+ * aligned. */
+typedef struct {
+  const float* box;          /* (B, A, 7) box codes */
+  const float* cls;          /* (B, A) class logits (one class per task) */
+  const float* dir;          /* (B, A, 2) direction logits */
+  const void* labels;        /* (B, A) int32 or int64 (cfg.labels_i64): -1 ignore, 0 negative, 1 positive */
+  const float* reg_targets;  /* (B, A, 7) encoded regression targets */
+  const float* anchors;      /* (B, A, 7) [x, y, z, w, l, h, r]; only the yaw is read */
+  float* grad_box;
+  float* grad_cls;
+  float* grad_dir;
+} sessd_supervised_task_t;
+
+/* Shapes and the constants of a SECOND / PointPillars config that sessd_supervised_loss needs. */
+typedef struct {
+  int32_t batch, num_anchors, num_tasks /* 1..4 */, labels_i64;
+  float pos_cls_weight, neg_cls_weight;             /* loss_norm (NormByNumPositives) */
+  float focal_alpha, focal_gamma, smooth_l1_sigma;  /* loss_cls, loss_bbox.sigma */
+  float cls_loss_weight, loc_loss_weight, dir_loss_weight, direction_offset;
+} sessd_supervised_loss_cfg_t;
+
 /* DI-NMS settings of sessd_predict (args->di): the arguments get_task_detections passes to box_torch_ops.rotate_weighted_nms
  * (mg_head_sessd.py:1012-1017: centerness_pow 2, nms_cnt_thresh 2.6, intervals (0, 20, 40, 60), sigma squares (0.0009, 0.009,
  * 0.1, 1), suppressed_thresh 0.3). interval[0 .. n_interval) are the distance bounds, sigma_sq[k] belongs to

@@ -400,6 +400,120 @@ class MultiGroupHead(nn.Module):
         out["overflow"] = int(r[R["overflow"]])
         return out
 
+    # ------------------------------------------------------------------ the plain supervised loss (no teacher), any number of tasks
+    def loss_supervised(self, example, preds_dicts, **kwargs):
+        """The supervised loss of det3d/models/bbox_heads/mg_head.py:559-652 (the reference's three-class SECOND and PointPillars
+        configs; no teacher, no ODIoU, no IoU prediction), per task: loss = weighted smooth-L1 localisation on the sin-encoded
+        yaw + weighted sigmoid focal classification + weighted softmax direction loss on the positives. Elementwise torch on
+        whatever device the inputs live on. Returns the reference's dict of per-task lists; the trainer sums `loss`."""
+        B = example["anchors"][0].shape[0]
+        keys = ("loss", "cls_pos_loss", "cls_neg_loss", "dir_loss_reduced", "cls_loss_reduced", "loc_loss_reduced", "loc_loss_elem",
+                "num_pos", "num_neg")
+        out = {k: [] for k in keys}
+        d = lambda v: v.detach().cpu()
+        for t, preds in enumerate(preds_dicts):
+            labels, reg_targets, nc = example["labels"][t], example["reg_targets"][t], self.num_classes[t]
+            cls_w, reg_w, cared = self.prepare_loss_weights(labels)
+            box = preds["box_preds"].view(B, -1, self.box_n_dim)
+            cls = preds["cls_preds"].view(B, -1, nc if self.encode_background_as_zeros else nc + 1)
+            one_hot = one_hot_f(labels * cared.type_as(labels), nc + 1, dtype=box.dtype)
+            if self.encode_background_as_zeros:
+                one_hot = one_hot[..., 1:]
+            enc_p, enc_t = add_sin_difference(box, reg_targets) if self.encode_rad_error_by_sin else (box, reg_targets)
+            loc = self.loss_reg(enc_p, enc_t, weights=reg_w)
+            focal = self.loss_cls(cls, one_hot, weights=cls_w)
+            loc_red = self.loss_reg._loss_weight * (loc.sum() / B)
+            cls_red = self.loss_cls._loss_weight * (focal.sum() / B)
+            pos_l, neg_l = _get_pos_neg_loss(focal, labels)
+            loss = loc_red + cls_red
+            dir_loss = None
+            if self.use_direction_classifier:
+                dir_targets = get_direction_target(example["anchors"][t], reg_targets, dir_offset=self.direction_offset)
+                w = (labels > 0).type_as(box)
+                w = w / torch.clamp(w.sum(-1, keepdim=True), min=1.0)
+                dir_loss = self.loss_aux(preds["dir_cls_preds"].view(B, -1, 2), dir_targets, weights=w).sum() / B
+                loss = loss + dir_loss * self.loss_aux._loss_weight
+            for k, v in (("loss", loss), ("cls_pos_loss", d(pos_l / self.loss_norm["pos_cls_weight"])),
+                         ("cls_neg_loss", d(neg_l / self.loss_norm["neg_cls_weight"])),
+                         ("dir_loss_reduced", None if dir_loss is None else d(dir_loss)), ("cls_loss_reduced", d(cls_red).mean()),
+                         ("loc_loss_reduced", d(loc_red).mean()), ("loc_loss_elem", [d(loc[:, :, i].sum() / B) for i in range(loc.shape[-1])]),
+                         ("num_pos", (labels > 0)[0].sum()), ("num_neg", (labels == 0)[0].sum())):
+                out[k].append(v)
+        return out
+
+    def supervised_loss_covers(self, example, preds_dicts):
+        """sessd_supervised_loss (csrc/supervised_loss.hip) covers: 1 to 4 tasks of one class each with the same number of anchors,
+        encode_background_as_zeros, NormByNumPositives, sin-encoded yaw, a softmax direction classifier with logit_scale 1, sigmoid
+        focal loss with an alpha, codewise smooth-L1, 7-number boxes, head outputs on the HIP device. Everything else runs
+        loss_supervised."""
+        T = len(preds_dicts)
+        if not (1 <= T <= ops.MAX_TASKS and T == len(self.num_classes) and all(n == 1 for n in self.num_classes)):
+            return False
+        if not (self.encode_background_as_zeros and self.loss_norm["type"] == "NormByNumPositives" and self.encode_rad_error_by_sin
+                and self.use_direction_classifier and getattr(self.loss_aux, "_logit_scale", 1.0) == 1.0
+                and type(self.loss_aux).__name__ == "WeightedSoftmaxClassificationLoss"
+                and type(self.loss_cls).__name__ == "SigmoidFocalLoss" and self.loss_cls._alpha is not None
+                and type(self.loss_reg).__name__ == "WeightedSmoothL1Loss" and self.loss_reg._codewise and self.box_n_dim == 7):
+            return False
+        if not all(k in example and len(example[k]) >= T for k in ("labels", "reg_targets", "anchors")):
+            return False
+        B = preds_dicts[0]["box_preds"].shape[0]
+        A = preds_dicts[0]["box_preds"].numel() // (B * 7)
+        for t, p in enumerate(preds_dicts):
+            if not all(k in p and p[k].is_cuda for k in ("box_preds", "cls_preds", "dir_cls_preds")):
+                return False
+            if p["box_preds"].numel() != B * A * 7 or p["cls_preds"].numel() != B * A or p["dir_cls_preds"].numel() != B * A * 2 \
+                    or example["labels"][t].numel() != B * A:
+                return False
+        return True
+
+    def loss_supervised_device(self, example, preds_dicts, unit_grad=False):
+        """loss_supervised summed over the tasks as one device op: returns (total, record) -- total = sum of the tasks' loss as an
+        autograd scalar of every task's box / cls / dir outputs (its backward hands over the kernel's gradients; iou_preds gets
+        none, the supervised loss has no such term), record = the (T + 1, 32) device log (ops.SUPERVISED_LOSS_RECORD names a task
+        row's entries; nothing is read back here)."""
+        if not self.supervised_loss_covers(example, preds_dicts):
+            raise ValueError("sessd_supervised_loss does not cover this head / these outputs (see supervised_loss_covers); "
+                             "use loss_supervised")
+        T = len(preds_dicts)
+        p0 = preds_dicts[0]["box_preds"]
+        B, dev = p0.shape[0], p0.device
+        A = p0.numel() // (B * 7)
+        ldt = example["labels"][0].dtype
+        ldt = ldt if ldt in (torch.int32, torch.int64) else torch.int64
+        key = (B, A, T, str(dev), ldt)
+        run = getattr(self, "_supervised_device_loss", None)
+        if run is None or run[0] != key:
+            cfg = dict(pos_cls_weight=self.loss_norm["pos_cls_weight"], neg_cls_weight=self.loss_norm["neg_cls_weight"],
+                       focal_alpha=self.loss_cls._alpha, focal_gamma=self.loss_cls._gamma or 0.0, smooth_l1_sigma=self.loss_reg._sigma,
+                       cls_loss_weight=self.loss_cls._loss_weight, loc_loss_weight=self.loss_reg._loss_weight,
+                       dir_loss_weight=self.loss_aux._loss_weight, direction_offset=self.direction_offset)
+            run = (key, ops.SupervisedLoss(B, A, T, dev, ldt == torch.int64, cfg))
+            self._supervised_device_loss = run
+        run = run[1]
+        C = lambda t: t if t.is_contiguous() else t.contiguous()
+        F = lambda t: C(t if t.dtype == torch.float32 else t.float())
+        targets = [dict(labels=C(example["labels"][t] if example["labels"][t].dtype == ldt else example["labels"][t].to(ldt)),
+                        reg_targets=F(example["reg_targets"][t]), anchors=F(example["anchors"][t])) for t in range(T)]
+        outs = []
+        for p in preds_dicts:
+            outs += [F(p["box_preds"]), F(p["cls_preds"]), F(p["dir_cls_preds"])]
+        return ops.SupervisedLossFunction.apply(run, targets, unit_grad, *outs)
+
+    def supervised_record_to_dict(self, rec):
+        """The device log record as the dict loss_supervised returns (one host read of (T + 1) x 32 floats); `loss` holds the
+        values only (the differentiable scalar is loss_supervised_device's total), `total` their sum."""
+        r = rec.detach().cpu()
+        R = ops.SUPERVISED_LOSS_RECORD
+        T = r.shape[0] - 1
+        out = {k: [r[t, R[k]].clone() for t in range(T)]
+               for k in ("loss", "cls_pos_loss", "cls_neg_loss", "dir_loss_reduced", "cls_loss_reduced", "loc_loss_reduced")}
+        out["loc_loss_elem"] = [[v.clone() for v in r[t, R["loc_loss_elem"]]] for t in range(T)]
+        for k in ("num_pos", "num_neg"):
+            out[k] = [r[t, R[k]].long() for t in range(T)]
+        out["total"] = r[T, 0].clone()
+        return out
+
     @torch.no_grad()
     def predict(self, example, preds_dicts, test_cfg, **kwargs):
         """Same contract as the reference: list (per sample) of dict(box3d_lidar, scores, label_preds, metadata).

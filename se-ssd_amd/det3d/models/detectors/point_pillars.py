@@ -1,7 +1,9 @@
 """PointPillars detector: pillar reader -> scatter to the BEV canvas -> neck -> head (+ predict), the inference surface of
 det3d/models/detectors/point_pillars.py:5-54 and single_stage.py:8-19. Same constructor kwargs and the reference's
 `forward(example, return_loss=True)` signature: `return_loss=False` returns `bbox_head.predict(...)`, a list of
-dict(box3d_lidar, scores, label_preds, metadata); `return_loss=True` raises NotImplementedError (inference only)."""
+dict(box3d_lidar, scores, label_preds, metadata); `return_loss=True` raises NotImplementedError (inference only) unless the model
+was switched to `supervised = True`: then it returns the supervised loss dict of `bbox_head.loss_supervised` (mg_head.py:559-652),
+and `forward_loss` gives the same loss as one scalar, from the device op sessd_supervised_loss where that covers the head."""
 from torch import nn
 
 from .. import builder
@@ -18,6 +20,10 @@ class PointPillars(nn.Module):
             self.neck = builder.build_neck(neck)
         self.bbox_head = builder.build_head(bbox_head)
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        # opt-in: the default keeps the inference-only contract (return_loss=True is refused by name), since neither TrainStep
+        # nor a captured iteration exists for this config yet; True enables forward(return_loss=True) and forward_loss
+        self.supervised = False
+        self.device_loss = True   # forward_loss: sessd_supervised_loss where it covers (False: the torch formulation)
 
     @property
     def with_neck(self):
@@ -31,7 +37,25 @@ class PointPillars(nn.Module):
     def forward(self, example, return_loss=True, **kwargs):
         data = dict(features=example["voxels"], num_voxels=example["num_points"], coors=example["coordinates"],
                     batch_size=len(example["num_voxels"]), input_shape=example["shape"][0])
-        if return_loss:
+        if return_loss and not self.supervised:
             raise NotImplementedError("PointPillars: inference only (return_loss=False); training of this config is not supported")
         preds = self.bbox_head(self.extract_feat(data))
+        if return_loss:
+            return self.bbox_head.loss_supervised(example, preds)
         return self.bbox_head.predict(example, preds, self.test_cfg)
+
+    def forward_loss(self, example, unit_grad=False):
+        """(total, record_or_dict): the supervised loss summed over the tasks as one differentiable scalar. Where
+        bbox_head.supervised_loss_covers (and device_loss is on) it is the device op, with its (T + 1, 32) device record
+        (bbox_head.supervised_record_to_dict reads it); otherwise the torch formulation with its dict. In train mode the pass
+        runs through the fused reader and neck as every forward does. Needs `supervised = True`."""
+        if not self.supervised:
+            raise NotImplementedError("PointPillars: inference only (return_loss=False); training of this config is not supported "
+                                      "unless the model is switched to supervised = True")
+        data = dict(features=example["voxels"], num_voxels=example["num_points"], coors=example["coordinates"],
+                    batch_size=len(example["num_voxels"]), input_shape=example["shape"][0])
+        preds = self.bbox_head(self.extract_feat(data))
+        if self.device_loss and self.bbox_head.supervised_loss_covers(example, preds):
+            return self.bbox_head.loss_supervised_device(example, preds, unit_grad=unit_grad)
+        ret = self.bbox_head.loss_supervised(example, preds)
+        return sum(ret["loss"]), ret

@@ -2,7 +2,10 @@
 det3d/models/detectors/voxelnet_sessd.py:7-43 and single_stage.py:8-19. Same constructor kwargs and the same
 `forward(example, is_ema=[False, None], return_loss=True)` contract:
   * `is_ema[0]` selects the un-augmented `*_raw` inputs (SE-SSD teacher pass) and returns raw head outputs,
-  * `return_loss=False` returns `bbox_head.predict(...)`: a list of dict(box3d_lidar, scores, label_preds, metadata)."""
+  * `return_loss=False` returns `bbox_head.predict(...)`: a list of dict(box3d_lidar, scores, label_preds, metadata),
+  * `return_loss=True` with teacher predictions in `is_ema[1]` returns the SE-SSD loss dict of `bbox_head.loss`; with
+    `is_ema[1] is None` (the reference's non-mean-teacher trainer call, e.g. the three-class config) the supervised loss dict
+    of `bbox_head.loss_supervised`."""
 from torch import nn
 
 from .. import builder
@@ -49,5 +52,7 @@ class VoxelNet(nn.Module):
         if teacher_pass:
             return preds
         if return_loss:
+            if teacher_preds is None:   # the non-mean-teacher trainer call: the plain supervised loss (mg_head.py:559-652)
+                return self.bbox_head.loss_supervised(example, preds)
             return self.bbox_head.loss(example, preds, teacher_preds)
         return self.bbox_head.predict(example, preds, self.test_cfg)

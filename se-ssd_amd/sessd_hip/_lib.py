@@ -48,6 +48,19 @@ class HeadLossCfg(C.Structure):
                 ("direction_offset", f32), ("score_thresh", f32), ("match_iou_thresh", f32), ("center_range", f32 * 6)]
 
 
+class SupervisedTask(C.Structure):
+    """sessd_supervised_task_t (include/sessd_hip_types.h)"""
+    _fields_ = [("box", vp), ("cls", vp), ("dir", vp), ("labels", vp), ("reg_targets", vp), ("anchors", vp), ("grad_box", vp),
+                ("grad_cls", vp), ("grad_dir", vp)]
+
+
+class SupervisedLossCfg(C.Structure):
+    """sessd_supervised_loss_cfg_t (include/sessd_hip_types.h)"""
+    _fields_ = [("batch", i32), ("num_anchors", i32), ("num_tasks", i32), ("labels_i64", i32), ("pos_cls_weight", f32),
+                ("neg_cls_weight", f32), ("focal_alpha", f32), ("focal_gamma", f32), ("smooth_l1_sigma", f32),
+                ("cls_loss_weight", f32), ("loc_loss_weight", f32), ("dir_loss_weight", f32), ("direction_offset", f32)]
+
+
 class DiCfg(C.Structure):
     """sessd_di_cfg_t (include/sessd_hip_types.h)"""
     _fields_ = [("cnt_thresh", f32), ("suppressed_thresh", f32), ("centerness_pow", f32), ("n_interval", i32),
@@ -96,6 +109,8 @@ SIGNATURES = {
     "sessd_bn2d_relu_train_bwd_apply": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
     "sessd_head_loss_workspace_bytes": (sz, [vp]),
     "sessd_head_loss": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "sessd_supervised_loss_workspace_bytes": (sz, [vp]),
+    "sessd_supervised_loss": (i32, [vp, vp, vp, vp, sz, vp]),
     "sessd_fill_u32": (i32, [vp, u32, sz, vp]),
     "sessd_fill_u32_multi": (i32, [i32, vp, vp, vp, vp]),
     "sessd_set_external_clear": (None, [i32]),

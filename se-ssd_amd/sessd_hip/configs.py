@@ -16,14 +16,16 @@ KITTI_3CLASS_ANCHORS = [dict(sizes=(1.6, 3.9, 1.56), z=-1.0, rotations=(0, 1.57)
 
 
 def kitti_3class_model():
-    """kitti_car_model() with tasks = [Car, Pedestrian, Cyclist]: inference only (the losses are single-task)."""
+    """kitti_car_model() with tasks = [Car, Pedestrian, Cyclist]; its loss is the supervised one (MultiGroupHead.loss_supervised /
+    loss_supervised_device), the SE-SSD loss and TrainStep are single-task."""
     return kitti_car_model(tasks=KITTI_3CLASS_TASKS)
 
 
 def kitti_3class_rpn_model():
     """The model dict of the reference's three-class config (examples/second/configs/
     kitti_all_vfev3_spmiddlefhd_rpn1_mghead_syncbn.py:62-115): the three one-class tasks on the SECOND-style RPN neck (one block
-    of 1 + 5 3x3 layers, one stride-1 up-sampler) instead of SSFA. Anchors: kitti_3class_anchors(). Inference only."""
+    of 1 + 5 3x3 layers, one stride-1 up-sampler) instead of SSFA. Anchors: kitti_3class_anchors(). VoxelNet.forward(example, is_ema=[False, None]) returns its
+    supervised loss; no TrainStep for it yet."""
     m = kitti_car_model(tasks=KITTI_3CLASS_TASKS)
     m["neck"] = dict(type="RPN", layer_nums=[5], ds_layer_strides=[1], ds_num_filters=[128], us_layer_strides=[1],
                      us_num_filters=[128], num_input_features=128, norm_cfg=None, logger=logging.getLogger("RPN"))
@@ -76,7 +78,7 @@ def kitti_pointpillars_model():
     """The model dict of the reference's PointPillars config (examples/point_pillars/configs/original_pp_mghead_syncbn_kitti.py:
     42-93): PillarFeatureNet (one 64-filter PFN layer; voxel_size / pc_range not passed -- the reader's defaults apply) ->
     PointPillarsScatter -> RPN with three blocks and up-samplers of stride 1 / 2 / 4 -> one Car task on 384 channels.
-    Inference only, through the det3d mirror."""
+    Through the det3d mirror; inference only unless the model is switched to `supervised = True` (PointPillars.forward_loss)."""
     m = kitti_car_model()
     m["type"] = "PointPillars"
     m["reader"] = dict(type="PillarFeatureNet", num_filters=[64], with_distance=False, norm_cfg=None)

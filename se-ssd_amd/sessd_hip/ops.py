@@ -2558,6 +2558,95 @@ class HeadLossFunction(torch.autograd.Function):
         return (*gs, None, None, None, None, None, None, None)
 
 
+SUPERVISED_LOSS_ROW = 32   # floats of one row of sessd_supervised_loss's record: one row per task, then the row of their sum
+SUPERVISED_LOSS_RECORD = {  # names of the floats of a task's row (include/sessd_hip.h); "total" is [0] of the last row
+    "loss": 0, "cls_loss_reduced": 1, "loc_loss_reduced": 2, "dir_loss_reduced": 3, "cls_pos_loss": 4, "cls_neg_loss": 5,
+    "loc_loss_elem": slice(6, 13), "num_pos": 13, "num_neg": 14, "positives": 15, "total": 0}
+
+
+class SupervisedLoss:
+    """The plain supervised multi-task head loss of MultiGroupHead.loss (mg_head.py:559-652: sigmoid focal classification,
+    smooth-L1 localisation on the sin-encoded yaw, softmax direction loss on the positives, NormByNumPositives) as ONE device op
+    (csrc/supervised_loss.hip: three launches for all tasks, nothing read back): value, log record and the gradient with respect
+    to every task's box / cls / dir outputs. Static buffers (allocated here, once): usable inside a captured iteration. One
+    object per (batch, anchors, tasks) shape and device. cfg: dict of the float fields of sessd_supervised_loss_cfg_t."""
+
+    def __init__(self, batch, num_anchors, num_tasks, device, labels_i64, cfg):
+        from ._lib import SupervisedLossCfg
+        self.B, self.A, self.T, self.dev = int(batch), int(num_anchors), int(num_tasks), device
+        c = SupervisedLossCfg()
+        c.batch, c.num_anchors, c.num_tasks, c.labels_i64 = self.B, self.A, self.T, 1 if labels_i64 else 0
+        for k in ("pos_cls_weight", "neg_cls_weight", "focal_alpha", "focal_gamma", "smooth_l1_sigma", "cls_loss_weight",
+                  "loc_loss_weight", "dir_loss_weight", "direction_offset"):
+            setattr(c, k, float(cfg[k]))
+        self.cfg = c
+        self._cfg_p = ctypes.addressof(c)
+        need = int(lib.sessd_supervised_loss_workspace_bytes(self._cfg_p))
+        if need == 0:
+            raise ValueError("sessd_supervised_loss does not cover this configuration (1 to %d tasks, batch and anchors >= 1)" % MAX_TASKS)
+        if torch.device(device).type != "cuda":
+            raise ValueError("SupervisedLoss needs the HIP device: there is no CPU fallback")
+        f = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=device)
+        self.ws = torch.zeros(need, dtype=torch.uint8, device=device)
+        self.g_box = [f(self.B, self.A, 7) for _ in range(self.T)]
+        self.g_cls = [f(self.B, self.A) for _ in range(self.T)]
+        self.g_dir = [f(self.B, self.A, 2) for _ in range(self.T)]
+        self.record = f(self.T + 1, SUPERVISED_LOSS_ROW)
+
+    def run(self, tasks):
+        """tasks: list of T dict(box, cls, dir, labels, reg_targets, anchors) of contiguous device tensors with B * A * (7, 1, 2,
+        1, 7, 7) elements. Returns the record tensor ((T + 1, 32), device); the gradients are in self.g_box / g_cls / g_dir."""
+        from ._lib import SupervisedTask
+        if len(tasks) != self.T:
+            raise ValueError("expected %d tasks, got %d" % (self.T, len(tasks)))
+        n = self.B * self.A
+        arr = (SupervisedTask * self.T)()
+        want_lab = torch.int64 if self.cfg.labels_i64 else torch.int32
+        for t, d in enumerate(tasks):
+            for k, per, dtype in (("box", 7, torch.float32), ("cls", 1, torch.float32), ("dir", 2, torch.float32), ("labels", 1, want_lab),
+                                  ("reg_targets", 7, torch.float32), ("anchors", 7, torch.float32)):
+                v = d[k]
+                if not v.is_cuda or v.dtype != dtype or not v.is_contiguous() or v.numel() != n * per:
+                    raise ValueError("task %d: %s must be a contiguous %s device tensor of %d x %d x %d elements, got %s %s %s"
+                                     % (t, k, dtype, self.B, self.A, per, v.device, v.dtype, tuple(v.shape)))
+                setattr(arr[t], k, v.data_ptr())
+            if d["dir"].data_ptr() % 8:
+                raise ValueError("task %d: dir must be 8-byte aligned" % t)
+            arr[t].grad_box, arr[t].grad_cls, arr[t].grad_dir = self.g_box[t].data_ptr(), self.g_cls[t].data_ptr(), self.g_dir[t].data_ptr()
+        check(lib.sessd_supervised_loss(self._cfg_p, ctypes.addressof(arr), self.record.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
+                                        _stream()), "supervised_loss")
+        return self.record
+
+
+class SupervisedLossFunction(torch.autograd.Function):
+    """total = the sum of the tasks' loss (SupervisedLoss record[T, 0]) as a differentiable scalar of the 3 * T head outputs
+    (box, cls, dir of task 0, then of task 1, ...). Returns (total, record). unit_grad=True: backward returns the kernel's
+    gradient buffers as they are (valid when the scalar itself is what `.backward()` is called on; no extra launches);
+    otherwise they are scaled by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, runner, targets, unit_grad, *outs):
+        if len(outs) != 3 * runner.T or len(targets) != runner.T:
+            raise ValueError("expected box, cls, dir of %d tasks" % runner.T)
+        tasks = [dict(targets[t], box=outs[3 * t].detach(), cls=outs[3 * t + 1].detach(), dir=outs[3 * t + 2].detach())
+                 for t in range(runner.T)]
+        rec = runner.run(tasks)
+        ctx.runner, ctx.unit, ctx.shapes = runner, bool(unit_grad), [o.shape for o in outs]
+        ctx.mark_non_differentiable(rec)
+        return rec[runner.T, 0].clone(), rec
+
+    @staticmethod
+    def backward(ctx, g, _g_rec):
+        r = ctx.runner
+        gs = []
+        for t in range(r.T):
+            gs += [r.g_box[t], r.g_cls[t], r.g_dir[t]]
+        gs = [v.view(sh) for v, sh in zip(gs, ctx.shapes)]
+        if not ctx.unit:
+            gs = [v * g for v in gs]
+        return (None, None, None, *gs)
+
+
 class _SumAll(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, scale):

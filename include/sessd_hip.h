@@ -643,6 +643,23 @@ int sessd_assign_targets(const float* anchors, int num_anchors, const float* gt_
                          float* bbox_outside_weights, int32_t* gt_id, void* workspace, size_t workspace_bytes,
                          sessd_stream_t stream);
 
+/* The same assignment for all frames and all tasks of a batch in three launches (clear of the per-ground-truth maxima, IoU
+ * pass, label pass; grid = (256-anchor blocks, B * T)), nothing read back: per (frame b, task t) the result is that of
+ * sessd_assign_targets on the rows k < gt_count[b] of gt_boxes[b] whose gt_classes equal tasks[t].class_id, in row order, with
+ * the task's anchors and thresholds, and label 1 for the positives -- same float32 operation order, same forced positives
+ * (bit equality with the ground truth's maximum), first argmax. gt_boxes (B, G, 7); gt_classes (B, G) or NULL (every live row
+ * belongs to every task); gt_count (B,) DEVICE int32 (clamped to [0, G]) or NULL (all G rows live). Rows at or beyond the
+ * count are never read. A (frame, task) without rows is all background with zero targets. tasks: HOST array of
+ * cfg->num_tasks entries; every output element is written.
+ * _workspace_bytes returns 0 and the entry SESSD_EINVAL before any device call for batch or num_anchors < 1, num_tasks outside
+ * 1..4, gt_capacity outside 1..128, batch * num_tasks > 65535, batch * num_tasks * num_anchors * 7 >= 2^31, null tasks /
+ * gt_boxes / workspace / anchors / labels / reg_targets, a workspace not aligned to 256 bytes; SESSD_EWORKSPACE for a workspace
+ * that is too small. Deterministic (the maximum is an integer atomicMax on the float bits); capturable in a hipGraph. */
+size_t sessd_assign_targets_batch_workspace_bytes(const sessd_assign_batch_cfg_t* cfg);
+int sessd_assign_targets_batch(const sessd_assign_batch_cfg_t* cfg, const sessd_assign_task_t* tasks, const float* gt_boxes,
+                               const int32_t* gt_classes, const int32_t* gt_count, void* workspace, size_t workspace_bytes,
+                               sessd_stream_t stream);
+
 /* ------------------------------------------------------------------ dense BEV neck + heads (a9-a10)
  * replace the ATen/cuDNN conv2d, conv_transpose2d, batch_norm, relu, softmax calls made by
  * det3d/models/necks/rpn_v1.py:220-235 (SSFA.forward; RPN.forward :107-116 uses the same layers) and

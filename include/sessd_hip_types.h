@@ -146,6 +146,25 @@ typedef struct {
   float cls_loss_weight, loc_loss_weight, dir_loss_weight, direction_offset;
 } sessd_supervised_loss_cfg_t;
 
+/* Shapes of sessd_assign_targets_batch: B frames, A anchors per task, T tasks (1..4), G ground-truth rows per frame (1..128). */
+typedef struct {
+  int32_t batch, num_anchors, num_tasks, gt_capacity;
+  int32_t labels_i64;        /* labels are int64 (else int32) */
+  int32_t anchors_per_frame; /* 0: every task's anchors are (A, 7), shared by the frames; else (B, A, 7) */
+} sessd_assign_batch_cfg_t;
+
+/* ONE task of sessd_assign_targets_batch: its anchors, its class, its thresholds and the tensors the call WRITES in every
+ * element. All device pointers. */
+typedef struct {
+  const float* anchors;      /* (A, 7), or (B, A, 7) when cfg.anchors_per_frame */
+  int32_t class_id;          /* rows with gt_classes == class_id are this task's; <= 0: every live row (enable_similar_type) */
+  float matched, unmatched;  /* positive at IoU >= matched, background below unmatched */
+  void* labels;              /* (B, A) int32 or int64 per cfg.labels_i64: -1 ignore, 0 background, 1 positive */
+  float* reg_targets;        /* (B, A, 7) */
+  float* reg_weights;        /* (B, A) or NULL */
+  int32_t* gt_id;            /* (B, A) or NULL: index among the task's rows of that frame in row order, -1 elsewhere */
+} sessd_assign_task_t;
+
 /* DI-NMS settings of sessd_predict (args->di): the arguments get_task_detections passes to box_torch_ops.rotate_weighted_nms
  * (mg_head_sessd.py:1012-1017: centerness_pow 2, nms_cnt_thresh 2.6, intervals (0, 20, 40, 60), sigma squares (0.0009, 0.009,
  * 0.1, 1), suppressed_thresh 0.3). interval[0 .. n_interval) are the distance bounds, sigma_sq[k] belongs to

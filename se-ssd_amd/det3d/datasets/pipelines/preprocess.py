@@ -246,7 +246,16 @@ class AssignTarget(object):
     target classes (yaw folded into [-pi, pi)), and per sample the assignment of create_target_np -- run on the MI355X
     (sessd_assign_targets) instead of numpy / numba in a DataLoader worker. Same result layout:
     res["lidar"]["targets"] = {anchors: [(70400,7)], labels: [(70400,)], reg_targets: [(70400,7)], reg_weights: [(70400,)],
-    positive_gt_id: [[(P,)]]} and the `targets_raw` twin from `annotations_raw`."""
+    positive_gt_id: [[(P,)]]} and the `targets_raw` twin from `annotations_raw`.
+    The map is cfg["feature_map_size"] where the assigner cfg has that key (PointPillars' head is 248 x 216), else the
+    reference's literal.
+    Several anchor generators with `target_assigner.tasks` (the three-class config): one generator per task -- the task gets its
+    generator's class name, thresholds and anchors, the ground truth is split by `gt_names` (every task takes every row with
+    enable_similar_type), labels are 1 -- and all tasks run as one sessd_assign_targets_batch call. Every entry of the result
+    is then a per-task list: targets[key][t], positive_gt_id[t] = [(P_t,)], and annotations' gt_boxes / gt_classes / gt_names
+    become per-task lists as well."""
+
+    MAX_GT = 128   # ground-truth rows of one frame (sessd_assign_targets_batch)
 
     def __init__(self, **kwargs):
         import torch
@@ -254,16 +263,67 @@ class AssignTarget(object):
         cfg = kwargs["cfg"]
         ta = cfg["target_assigner"]
         gens = ta["anchor_generators"]
-        assert len(gens) == 1, "single anchor generator (config.py:84-94)"
+        self.enable_similar_type = _get(cfg, "enable_similar_type", False)
+        self.out_size_factor = _get(cfg, "out_size_factor", 8)
+        self.feature_map_size = [int(v) for v in (_get(cfg, "feature_map_size", None) or [1, 200, 176])]
+        make = lambda g: create_anchors_3d_range(self.feature_map_size, g["anchor_ranges"], g["sizes"], g["rotations"]).reshape(-1, 7)
+        self._torch = torch
+        self._dev_anchors = None
+        self.multi = len(gens) > 1
+        if self.multi:
+            tasks = _get(ta, "tasks", None)
+            if tasks is None:
+                raise ValueError("several anchor generators need target_assigner.tasks")
+            if any(int(t["num_class"]) != 1 for t in tasks) or len(tasks) != len(gens):
+                raise ValueError("AssignTarget supports one anchor generator per task: %d generators for tasks of %s classes"
+                                 % (len(gens), [int(t["num_class"]) for t in tasks]))
+            if len(tasks) > 4:
+                raise ValueError("AssignTarget supports at most 4 tasks, got %d" % len(tasks))
+            self.target_class_names = [g["class_name"] for g in gens]
+            self.thresholds = [(float(g["matched_threshold"]), float(g["unmatched_threshold"])) for g in gens]
+            self.anchors_by_task = [make(g) for g in gens]
+            self._batched = None
+            return
         g = gens[0]
         self.target_class_names = [g["class_name"]]
-        self.enable_similar_type = _get(cfg, "enable_similar_type", False)
         self.target_class_ids = [1, 2] if self.enable_similar_type else [1]
         self.matched, self.unmatched = float(g["matched_threshold"]), float(g["unmatched_threshold"])
-        self.out_size_factor = _get(cfg, "out_size_factor", 8)
-        self.anchors = create_anchors_3d_range((1, 200, 176), g["anchor_ranges"], g["sizes"], g["rotations"]).reshape(-1, 7)
-        self._dev_anchors = None
-        self._torch = torch
+        self.anchors = make(g)
+
+    def _targets_of_tasks(self, gt_dict):
+        """the multi-task path: one device call for all tasks of the frame"""
+        from sessd_hip import ops
+        torch = self._torch
+        T, G = len(self.target_class_names), self.MAX_GT
+        if self._batched is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            tasks = [dict(anchors=torch.from_numpy(a).to(dev), class_id=0 if self.enable_similar_type else t + 1, matched_threshold=m,
+                          unmatched_threshold=u) for t, (a, (m, u)) in enumerate(zip(self.anchors_by_task, self.thresholds))]
+            self._batched = ops.AssignTargets(1, self.anchors_by_task[0].shape[0], tasks, dev, gt_capacity=G)
+        names = np.asarray(gt_dict["gt_names"])
+        boxes = np.ascontiguousarray(gt_dict["gt_boxes"], np.float32).reshape(-1, 7).copy()
+        boxes[:, -1] = boxes[:, -1] - np.floor(boxes[:, -1] / (2 * np.pi) + 0.5) * (2 * np.pi)  # limit_period(ry, 0.5, 2 pi)
+        task_of = np.zeros(len(names), np.int32)   # 1 + task index, 0: a row of no task
+        for t, n in enumerate(self.target_class_names):
+            task_of[names == n] = t + 1
+        live = np.ones(len(names), bool) if self.enable_similar_type else task_of > 0
+        if int(live.sum()) > G:
+            raise ValueError("AssignTarget holds at most %d ground-truth rows of the target classes per frame, got %d" % (G, int(live.sum())))
+        m = int(live.sum())
+        host = np.zeros((1, G, 7), np.float32)
+        cls = np.zeros((1, G), np.int32)
+        host[0, :m], cls[0, :m] = boxes[live], task_of[live]
+        dev = self._batched.dev
+        r = self._batched.run(torch.from_numpy(host).to(dev), torch.from_numpy(cls).to(dev),
+                              torch.tensor([m], dtype=torch.int32).to(dev))
+        rows = [np.ones(len(names), bool) if self.enable_similar_type else task_of == t + 1 for t in range(T)]
+        classes = np.asarray(gt_dict["gt_classes"])
+        gt_dict["gt_boxes"], gt_dict["gt_classes"], gt_dict["gt_names"] = [boxes[k] for k in rows], [classes[k] for k in rows], [names[k] for k in rows]
+        gid = [r["gt_id"][t][0].cpu().numpy() for t in range(T)]
+        return {"labels": [r["labels"][t][0].cpu().numpy() for t in range(T)],
+                "reg_targets": [r["reg_targets"][t][0].cpu().numpy() for t in range(T)],
+                "reg_weights": [r["reg_weights"][t][0].cpu().numpy() for t in range(T)],
+                "positive_gt_id": [[g[g >= 0]] for g in gid]}
 
     def _assign(self, gt_boxes, gt_names):
         from sessd_hip import ops
@@ -279,7 +339,9 @@ class AssignTarget(object):
                     bbox_outside_weights=r["bbox_outside_weights"].cpu().numpy(), positive_gt_id=[gid[gid >= 0]])
 
     def _targets_of(self, gt_dict):
-        mask = np.isin(gt_dict["gt_classes"], self.target_class_ids)
+        if self.multi:
+            return self._targets_of_tasks(gt_dict)
+        mask =np.isin(gt_dict["gt_classes"], self.target_class_ids)
         boxes = gt_dict["gt_boxes"][mask]
         boxes[:, -1] = boxes[:, -1] - np.floor(boxes[:, -1] / (2 * np.pi) + 0.5) * (2 * np.pi)  # limit_period(ry, 0.5, 2 pi)
         gt_dict["gt_boxes"], gt_dict["gt_classes"], gt_dict["gt_names"] = [boxes], [gt_dict["gt_classes"][mask]], [gt_dict["gt_names"][mask]]
@@ -288,8 +350,9 @@ class AssignTarget(object):
                 "positive_gt_id": [t["positive_gt_id"]]}
 
     def __call__(self, res, info):
-        targets = {"anchors": [self.anchors]}
-        targets_raw = {"anchors": [self.anchors]}
+        anchors = list(self.anchors_by_task) if self.multi else [self.anchors]
+        targets = {"anchors": anchors}
+        targets_raw = {"anchors": list(anchors)}
         if res["mode"] == "train" and res.get("labeled", True):
             targets.update(self._targets_of(res["lidar"]["annotations"]))
             if "annotations_raw" in res["lidar"]:

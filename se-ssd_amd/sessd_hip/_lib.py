@@ -61,6 +61,18 @@ class SupervisedLossCfg(C.Structure):
                 ("cls_loss_weight", f32), ("loc_loss_weight", f32), ("dir_loss_weight", f32), ("direction_offset", f32)]
 
 
+class AssignBatchCfg(C.Structure):
+    """sessd_assign_batch_cfg_t (include/sessd_hip_types.h)"""
+    _fields_ = [("batch", i32), ("num_anchors", i32), ("num_tasks", i32), ("gt_capacity", i32), ("labels_i64", i32),
+                ("anchors_per_frame", i32)]
+
+
+class AssignTask(C.Structure):
+    """sessd_assign_task_t (include/sessd_hip_types.h)"""
+    _fields_ = [("anchors", vp), ("class_id", i32), ("matched", f32), ("unmatched", f32), ("labels", vp), ("reg_targets", vp),
+                ("reg_weights", vp), ("gt_id", vp)]
+
+
 class DiCfg(C.Structure):
     """sessd_di_cfg_t (include/sessd_hip_types.h)"""
     _fields_ = [("cnt_thresh", f32), ("suppressed_thresh", f32), ("centerness_pow", f32), ("n_interval", i32),
@@ -225,6 +237,8 @@ SIGNATURES = {
     "sessd_conv2d_wgrad_any_width": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
     "sessd_assign_targets_workspace_bytes": (sz, [i32]),
     "sessd_assign_targets": (i32, [vp, i32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, sz, vp]),
+    "sessd_assign_targets_batch_workspace_bytes": (sz, [vp]),
+    "sessd_assign_targets_batch": (i32, [vp, vp, vp, vp, vp, vp, sz, vp]),
     "sessd_odiou3d": (i32, [vp, vp, i32, vp, vp, vp]),
     "sessd_adam_ema_step": (i32, [vp, vp, vp, vp, vp, sz, f64, f64, f64, f64, f64, i32, vp, f64, vp]),
     "sessd_one_cycle_args": (i32, [vp, i32, f64, f64, f64, f64, f64, f64, f64, f64, vp, vp, vp]),

@@ -41,6 +41,38 @@ def kitti_3class_anchors(feature_hw=(200, 176), voxel_range=None):
     return create_task_anchors(feature_hw, KITTI_3CLASS_ANCHORS, (r[0], r[1], r[3], r[4]))
 
 
+def _anchor_generator(class_name, sizes, z, matched, unmatched):
+    return dict(type="anchor_generator_range", sizes=list(sizes), anchor_ranges=[0, -40.0, z, 70.4, 40.0, z], rotations=[0, 1.57],
+                matched_threshold=matched, unmatched_threshold=unmatched, class_name=class_name)
+
+
+_BOX_CODER = dict(type="ground_box3d_coder", n_dim=7, linear_dim=False, encode_angle_vector=False)
+
+# The `assigner` dict (train_cfg.assigner, what the AssignTarget stage takes as cfg) of the reference's three-class config
+# (examples/second/configs/kitti_all_vfev3_spmiddlefhd_rpn1_mghead_syncbn.py:19-55,117-122): one anchor generator per task on
+# the [1, 200, 176] map, Car at 0.6 / 0.45, Pedestrian and Cyclist at 0.4 / 0.2.
+ASSIGNER_3CLASS = dict(
+    box_coder=_BOX_CODER,
+    target_assigner=dict(type="iou", anchor_generators=[
+        _anchor_generator("Car", KITTI_3CLASS_ANCHORS[0]["sizes"], KITTI_3CLASS_ANCHORS[0]["z"], 0.6, 0.45),
+        _anchor_generator("Pedestrian", KITTI_3CLASS_ANCHORS[1]["sizes"], KITTI_3CLASS_ANCHORS[1]["z"], 0.4, 0.2),
+        _anchor_generator("Cyclist", KITTI_3CLASS_ANCHORS[2]["sizes"], KITTI_3CLASS_ANCHORS[2]["z"], 0.4, 0.2)],
+        sample_positive_fraction=-1, sample_size=512, region_similarity_calculator=dict(type="nearest_iou_similarity"),
+        pos_area_threshold=-1, tasks=KITTI_3CLASS_TASKS),
+    out_size_factor=8, debug=False)
+
+# The same of the PointPillars config (examples/point_pillars/configs/original_pp_mghead_syncbn_kitti.py:17-35,95-99): the car
+# generator on the config's own anchor range, and the map its head really has -- the reference's stage hard-codes
+# [1, 200, 176], which is not the 248 x 216 output of this neck.
+ASSIGNER_POINTPILLARS = dict(
+    box_coder=_BOX_CODER,
+    target_assigner=dict(type="iou", anchor_generators=[_anchor_generator("Car", (1.6, 3.9, 1.56), -1.0, 0.6, 0.45)],
+                         sample_positive_fraction=-1, sample_size=512,
+                         region_similarity_calculator=dict(type="nearest_iou_similarity"), pos_area_threshold=-1,
+                         tasks=[dict(num_class=1, class_names=["Car"])]),
+    out_size_factor=2, feature_map_size=[1, 248, 216])
+
+
 def kitti_car_model(tasks=None):
     tasks = [dict(num_class=1, class_names=["Car"])] if tasks is None else [dict(t) for t in tasks]
     box_coder = dict(type="ground_box3d_coder", n_dim=7, linear_dim=False, encode_angle_vector=False)

@@ -2433,6 +2433,103 @@ def assign_targets(anchors, gt_boxes, gt_classes=None, matched_threshold=0.6, un
     return out
 
 
+ASSIGN_MAX_TASKS = 4   # sessd_assign_targets_batch: tasks per call
+ASSIGN_MAX_GT = 128    # and ground-truth rows per frame
+
+
+class AssignTargets:
+    """Anchor target assignment for all frames and all tasks of a batch as ONE device op (sessd_assign_targets_batch: one clear
+    and two launches, the ground-truth counts read on the device, nothing read back). Per (frame, task) the result is that of
+    assign_targets() on the frame's live rows of the task's class with the task's thresholds; labels are 1 on the positives.
+    tasks: list of dict(anchors (A, 7) or (B, A, 7) float32 on `device`, class_id, matched_threshold, unmatched_threshold);
+    class_id <= 0 takes every live row. Outputs and workspace are allocated here, once: usable inside a captured iteration.
+    `labels`, `reg_targets` and `anchors` of the result are what MultiGroupHead.loss_supervised / loss_supervised_device take."""
+
+    _OUT = ("labels", "reg_targets", "reg_weights", "gt_id")
+
+    def __init__(self, batch, num_anchors, tasks, device, gt_capacity=128, labels_i64=False):
+        from ._lib import AssignBatchCfg
+        self.B, self.A, self.T, self.G = int(batch), int(num_anchors), len(tasks), int(gt_capacity)
+        self.dev = torch.device(device)
+        if not 1 <= self.T <= ASSIGN_MAX_TASKS:
+            raise ValueError("AssignTargets takes 1 to %d tasks, got %d" % (ASSIGN_MAX_TASKS, self.T))
+        if not 1 <= self.G <= ASSIGN_MAX_GT:
+            raise ValueError("AssignTargets holds 1 to %d ground-truth rows per frame, got gt_capacity = %d" % (ASSIGN_MAX_GT, self.G))
+        if self.dev.type != "cuda":
+            raise ValueError("AssignTargets needs the HIP device: there is no CPU fallback")
+        per_frame = {t["anchors"].dim() == 3 for t in tasks}
+        if len(per_frame) != 1:
+            raise ValueError("the tasks' anchors must all be (A, 7) or all be (B, A, 7)")
+        self.per_frame = per_frame.pop()
+        want = (self.B, self.A, 7) if self.per_frame else (self.A, 7)
+        self.tasks = []
+        for t, d in enumerate(tasks):
+            a = d["anchors"]
+            if not a.is_cuda or a.dtype != torch.float32 or tuple(a.shape) != want:
+                raise ValueError("task %d: anchors must be a float32 device tensor of shape %s, got %s %s %s"
+                                 % (t, want, a.device, a.dtype, tuple(a.shape)))
+            self.tasks.append(dict(anchors=a.contiguous(), class_id=int(d["class_id"]), matched=float(d["matched_threshold"]),
+                                   unmatched=float(d["unmatched_threshold"])))
+        c = AssignBatchCfg(self.B, self.A, self.T, self.G, 1 if labels_i64 else 0, 1 if self.per_frame else 0)
+        self.cfg, self._cfg_p = c, ctypes.addressof(c)
+        need = int(lib.sessd_assign_targets_batch_workspace_bytes(self._cfg_p))
+        if need == 0:
+            raise ValueError("sessd_assign_targets_batch does not cover this shape (batch and anchors >= 1, batch x tasks <= 65535, "
+                             "batch x tasks x anchors x 7 < 2^31)")
+        self.label_dtype = torch.int64 if labels_i64 else torch.int32
+        z = lambda shape, dt: [torch.zeros(shape, dtype=dt, device=self.dev) for _ in range(self.T)]
+        self.ws = torch.zeros(need, dtype=torch.uint8, device=self.dev)
+        self.out = dict(labels=z((self.B, self.A), self.label_dtype), reg_targets=z((self.B, self.A, 7), torch.float32),
+                        reg_weights=z((self.B, self.A), torch.float32), gt_id=z((self.B, self.A), torch.int32))
+        # (B, A, 7) per task as the head loss reads them: made once and contiguous, so that no call (or replay) copies them
+        self.anchors = [d["anchors"] if self.per_frame else d["anchors"].unsqueeze(0).repeat(self.B, 1, 1) for d in self.tasks]
+
+    def _check(self, v, name, dtype, shape):
+        if not v.is_cuda or v.dtype != dtype or tuple(v.shape) != shape or not v.is_contiguous():
+            raise ValueError("%s must be a contiguous %s device tensor of shape %s, got %s %s %s"
+                             % (name, dtype, shape, v.device, v.dtype, tuple(v.shape)))
+
+    def run(self, gt_boxes, gt_classes=None, gt_count=None, out=None):
+        """gt_boxes (B, G, 7) float32, gt_classes (B, G) int32 or None (every live row belongs to every task), gt_count (B,)
+        int32 DEVICE tensor or None (all G rows live). out: dict with any of labels / reg_targets / reg_weights / gt_id, each
+        a list of T tensors (or None entries) written in place of this object's own; a key given as False is not computed
+        (reg_weights, gt_id). Returns dict(labels, reg_targets, reg_weights, gt_id, anchors), each a list of T tensors."""
+        from ._lib import AssignTask
+        B, A, T, G = self.B, self.A, self.T, self.G
+        self._check(gt_boxes, "gt_boxes", torch.float32, (B, G, 7))
+        if gt_classes is not None:
+            self._check(gt_classes, "gt_classes", torch.int32, (B, G))
+        if gt_count is not None:
+            self._check(gt_count, "gt_count", torch.int32, (B,))
+        shapes = dict(labels=((B, A), self.label_dtype), reg_targets=((B, A, 7), torch.float32), reg_weights=((B, A), torch.float32),
+                      gt_id=((B, A), torch.int32))
+        res = {}
+        for k in self._OUT:
+            given = None if out is None else out.get(k)
+            if given is False:
+                if k in ("labels", "reg_targets"):
+                    raise ValueError("%s is always written" % k)
+                res[k] = [None] * T
+                continue
+            if given is None:
+                res[k] = list(self.out[k])
+                continue
+            if len(given) != T:
+                raise ValueError("out[%r] must list %d tensors, got %d" % (k, T, len(given)))
+            res[k] = [self.out[k][t] if v is None else v for t, v in enumerate(given)]
+            for t, v in enumerate(res[k]):
+                self._check(v, "out[%r][%d]" % (k, t), shapes[k][1], shapes[k][0])
+        arr = (AssignTask * T)()
+        for t, d in enumerate(self.tasks):
+            arr[t].anchors, arr[t].class_id, arr[t].matched, arr[t].unmatched = d["anchors"].data_ptr(), d["class_id"], d["matched"], d["unmatched"]
+            arr[t].labels, arr[t].reg_targets = res["labels"][t].data_ptr(), res["reg_targets"][t].data_ptr()
+            arr[t].reg_weights, arr[t].gt_id = _p(res["reg_weights"][t]) or None, _p(res["gt_id"][t]) or None
+        check(lib.sessd_assign_targets_batch(self._cfg_p, ctypes.addressof(arr), gt_boxes.data_ptr(), _p(gt_classes) or None,
+                                             _p(gt_count) or None, self.ws.data_ptr(), self.ws.numel(), _stream()), "assign_targets_batch")
+        res["anchors"] = list(self.anchors)
+        return res
+
+
 class OdiouFunction(torch.autograd.Function):
     """ODIoU loss of odious.py:837-900 on the device: loss = 2 * sum(weights * term) / batch_size, differentiable with
     respect to the predicted boxes (the kernel returns the per-pair gradient with the value)."""

@@ -68,6 +68,10 @@ class DeviceBatcher:
     many batches can be drawn: their scene choices and augmentation parameters are drawn here, once, from `seed`."""
 
     M = 15  # boxes per scene (visible ones first; the rest parked at FAR)
+    # True: load() assigns the targets of a view for all frames in one ops.AssignTargets call that writes into the example,
+    # instead of one ops.assign_targets call and two copies per frame and view (profiles/assign_targets_batch.json)
+    batched_targets = False
+    _assigner = None
 
     def __init__(self, pool, dev, batch=4, iterations=1000, max_voxels=16000, seed=0, augment=True):
         from .anchors import create_anchors_3d_range
@@ -190,13 +194,21 @@ class DeviceBatcher:
             ex["coordinates" + sfx].copy_(torch.where(live[:, None], r["coors"], -1))
             ex["num_points" + sfx].copy_(torch.where(live, r["num_points"], 1))
             ex["num_voxels_dev" + sfx].copy_(n)
-        for b, i in enumerate(idx):
-            gt_raw = self._in_range(self.boxes[i])
-            gt_stu = self._in_range(self._student_boxes(self.boxes[i], self.par[it, b]))
-            for gt, L, R in ((gt_stu, "labels", "reg_targets"), (gt_raw, "labels_raw", "reg_targets_raw")):
-                tg = ops.assign_targets(self.anchors, gt, None, 0.6, 0.45)
-                ex[L][0][b].copy_(tg["labels"])
-                ex[R][0][b].copy_(tg["bbox_targets"])
+        gt_raw = [self._in_range(self.boxes[i]) for i in idx]
+        gt_stu = [self._in_range(self._student_boxes(self.boxes[i], self.par[it, b])) for b, i in enumerate(idx)]
+        if self.batched_targets:
+            # one sessd_assign_targets_batch call per view, written straight into the example: same bits as the loop below
+            if self._assigner is None:
+                self._assigner = ops.AssignTargets(B, self.anchors.shape[0], [dict(anchors=self.anchors, class_id=0, matched_threshold=0.6,
+                                                                                  unmatched_threshold=0.45)], self.dev, gt_capacity=self.M)
+            for gts, L, R in ((gt_stu, "labels", "reg_targets"), (gt_raw, "labels_raw", "reg_targets_raw")):
+                self._assigner.run(torch.stack(gts), out=dict(labels=[ex[L][0]], reg_targets=[ex[R][0]], reg_weights=False, gt_id=False))
+        else:
+            for b in range(B):
+                for gt, L, R in ((gt_stu[b], "labels", "reg_targets"), (gt_raw[b], "labels_raw", "reg_targets_raw")):
+                    tg = ops.assign_targets(self.anchors, gt, None, 0.6, 0.45)
+                    ex[L][0][b].copy_(tg["labels"])
+                    ex[R][0][b].copy_(tg["bbox_targets"])
         ex["transformation_dev"].copy_(self.par[it])
         return ex
 

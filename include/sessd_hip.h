@@ -660,6 +660,28 @@ int sessd_assign_targets_batch(const sessd_assign_batch_cfg_t* cfg, const sessd_
                                const int32_t* gt_classes, const int32_t* gt_count, void* workspace, size_t workspace_bytes,
                                sessd_stream_t stream);
 
+/* One training batch's clouds and ground truth drawn from resident scene tables in two launches (csrc/draw_batch.hip): the
+ * global augmentation of the reference's Preprocess (flip about the x axis, rotation about z, scaling) and Voxelization's
+ * ground-truth range filter, for all frames at once, nothing read back.
+ * Tables (device): pool_points (S, P, 4) with pool_point_count (S); pool_boxes (S, G, 7), pool_classes (S, G) and
+ * pool_box_count (S); choice (T, B) int32 = the scene of each slot of each iteration; par (T, B, 5) rows
+ * [flipped, cos, sin, rotation, scale]. The row of choice / par used is (iter_dev ? *iter_dev : iter_host) mod T (iter_dev: a
+ * DEVICE int32 or NULL). range_xy: HOST [x_lo, y_lo, x_hi, y_hi].
+ * Outputs (device), every element written: staged (B, P, 4) -- a row below the scene's count moved as
+ * y' = flipped ? -y : y, X = (x c + y' s) k, Y = ((-x) s + y' c) k, Z = z k, r kept; a row at or beyond it the out-of-range row
+ * of sessd_stage_points --; gt_boxes (B, G, 7), gt_classes (B, G), gt_count (B): the live boxes moved (centre as the points,
+ * columns 2..5 times k, yaw = (flipped ? -yaw + float32(pi) : yaw) + rotation), kept when any of the four BEV corners lies
+ * strictly inside range_xy, compacted in row order, zeros behind the count; transformation (B, 5) = the par rows used.
+ * Every product and sum is rounded once (no FMA contraction). Counts are clamped to [0, P] / [0, G]; a scene index outside
+ * [0, S) draws an empty frame. SESSD_EINVAL before any device call for S, P, G, T or B < 1, G > 128, B > 65535, S * P or
+ * B * P >= 2^29, T * B >= 2^28, a null pointer (iter_dev excepted), pool_points or staged not aligned to 16 bytes.
+ * Deterministic; capturable in a hipGraph. */
+int sessd_draw_batch(const float* pool_points, const int32_t* pool_point_count, const float* pool_boxes, const int32_t* pool_classes,
+                     const int32_t* pool_box_count, const int32_t* choice, const float* par, int num_scenes, int points_per_scene,
+                     int boxes_per_scene, int num_iterations, int batch, const float* range_xy, int iter_host, const int32_t* iter_dev,
+                     float* staged, float* gt_boxes, int32_t* gt_classes, int32_t* gt_count, float* transformation,
+                     sessd_stream_t stream);
+
 /* ------------------------------------------------------------------ dense BEV neck + heads (a9-a10)
  * replace the ATen/cuDNN conv2d, conv_transpose2d, batch_norm, relu, softmax calls made by
  * det3d/models/necks/rpn_v1.py:220-235 (SSFA.forward; RPN.forward :107-116 uses the same layers) and

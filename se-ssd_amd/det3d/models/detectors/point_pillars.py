@@ -20,8 +20,8 @@ class PointPillars(nn.Module):
             self.neck = builder.build_neck(neck)
         self.bbox_head = builder.build_head(bbox_head)
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
-        # opt-in: the default keeps the inference-only contract (return_loss=True is refused by name), since neither TrainStep
-        # nor a captured iteration exists for this config yet; True enables forward(return_loss=True) and forward_loss
+        # opt-in: the default keeps the inference-only contract (return_loss=True is refused by name); True enables
+        # forward(return_loss=True) and forward_loss, which sessd_hip.train.SupervisedTrainStep runs and captures
         self.supervised = False
         self.device_loss = True   # forward_loss: sessd_supervised_loss where it covers (False: the torch formulation)
 
@@ -30,13 +30,19 @@ class PointPillars(nn.Module):
         return getattr(self, "neck", None) is not None
 
     def extract_feat(self, data):
-        input_features = self.reader(data["features"], data["num_voxels"], data["coors"])
-        x = self.backbone(input_features, data["coors"], data["batch_size"], data["input_shape"])
+        n_dev = data.get("num_voxels_dev")
+        if n_dev is None:
+            input_features = self.reader(data["features"], data["num_voxels"], data["coors"])
+            x = self.backbone(input_features, data["coors"], data["batch_size"], data["input_shape"])
+        else:   # capacity form: fixed-size tables, the live pillar count on the device (a captured iteration replays on it)
+            input_features = self.reader(data["features"], data["num_voxels"], data["coors"], num_voxels_dev=n_dev)
+            x = self.backbone(input_features, data["coors"], data["batch_size"], data["input_shape"], num_voxels_dev=n_dev)
         return self.neck(x) if self.with_neck else x
 
     def forward(self, example, return_loss=True, **kwargs):
         data = dict(features=example["voxels"], num_voxels=example["num_points"], coors=example["coordinates"],
-                    batch_size=len(example["num_voxels"]), input_shape=example["shape"][0])
+                    batch_size=len(example["num_voxels"]), input_shape=example["shape"][0],
+                    num_voxels_dev=example.get("num_voxels_dev"))
         if return_loss and not self.supervised:
             raise NotImplementedError("PointPillars: inference only (return_loss=False); training of this config is not supported")
         preds = self.bbox_head(self.extract_feat(data))
@@ -53,7 +59,8 @@ class PointPillars(nn.Module):
             raise NotImplementedError("PointPillars: inference only (return_loss=False); training of this config is not supported "
                                       "unless the model is switched to supervised = True")
         data = dict(features=example["voxels"], num_voxels=example["num_points"], coors=example["coordinates"],
-                    batch_size=len(example["num_voxels"]), input_shape=example["shape"][0])
+                    batch_size=len(example["num_voxels"]), input_shape=example["shape"][0],
+                    num_voxels_dev=example.get("num_voxels_dev"))
         preds = self.bbox_head(self.extract_feat(data))
         if self.device_loss and self.bbox_head.supervised_loss_covers(example, preds):
             return self.bbox_head.loss_supervised_device(example, preds, unit_grad=unit_grad)

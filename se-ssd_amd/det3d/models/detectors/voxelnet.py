@@ -46,6 +46,17 @@ class VoxelNet(nn.Module):
                                      input_shape=shape[0], n_dev=example.get("num_voxels_dev" + suffix)))
         return self.bbox_head(bev)
 
+    def forward_loss(self, example, unit_grad=False):
+        """(total, record_or_dict) of the supervised loss without teacher predictions, with the meaning of
+        PointPillars.forward_loss: where bbox_head.supervised_loss_covers it is the device op sessd_supervised_loss with its
+        (T + 1, 32) device record, otherwise the torch formulation with its dict. A capacity-form example
+        (`num_voxels_dev`) runs the backbone in its capacity mode, as every pass does."""
+        preds = self.forward_preds(example)
+        if getattr(self, "device_loss", True) and self.bbox_head.supervised_loss_covers(example, preds):
+            return self.bbox_head.loss_supervised_device(example, preds, unit_grad=unit_grad)
+        ret = self.bbox_head.loss_supervised(example, preds)
+        return sum(ret["loss"]), ret
+
     def forward(self, example, is_ema=[False, None], return_loss=True, **kwargs):
         teacher_pass, teacher_preds = is_ema[0], is_ema[1]
         preds = self.forward_preds(example, raw=teacher_pass)

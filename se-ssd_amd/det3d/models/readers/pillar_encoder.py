@@ -79,20 +79,26 @@ class PillarFeatureNet(nn.Module):
                 and pfn.units == ops.PILLAR_CHANNELS and type(pfn.norm) is nn.BatchNorm1d
                 and features.shape[0] * features.shape[1] >= 2)
 
-    def forward(self, features, num_voxels, coors):
+    def forward(self, features, num_voxels, coors, num_voxels_dev=None):
         """features (N, T, 4), num_voxels (N,) points per pillar, coors (N, 4) [b, z, y, x] -> (N, C). The reference's trailing
-        `.squeeze()` collapses N = 1 to (C,); this returns (N, C) always."""
+        `.squeeze()` collapses N = 1 to (C,); this returns (N, C) always. num_voxels_dev (device int32[1]): capacity form -- only
+        the rows below it are pillars; the rest enter neither the features (zero rows) nor the batch statistics nor a gradient.
+        The kernels read the count on the device; the torch formulation cannot, so capacity form needs the device path."""
         pfn = self.pfn_layers[0]
         if self.on_device_train_path(features):
             return ops.pillar_features_train(features.float().contiguous(), num_voxels.int().contiguous(), coors.int().contiguous(),
                                              pfn.linear.weight, pfn.norm, self.vx, self.vy, self.x_offset, self.y_offset,
-                                             with_distance=self._with_distance)
+                                             with_distance=self._with_distance, num_voxels_dev=num_voxels_dev)
         if not self.on_device_path(features):
+            if num_voxels_dev is not None:
+                raise ValueError("PillarFeatureNet: capacity form (num_voxels_dev) needs the device path -- one PFN layer of %d "
+                                 "channels on a device tensor; the torch formulation would count the padded rows" % ops.PILLAR_CHANNELS)
             return self._forward_torch(features, num_voxels, coors)
         scale, shift = fold_bn(pfn.norm)
+        # (with a count, pillar_features leaves the rows beyond it unwritten: they are the scatter's to skip)
         return ops.pillar_features(features.float().contiguous(), num_voxels.int().contiguous(), coors.int().contiguous(),
                                    pfn.linear.weight.detach().float().contiguous(), scale, shift, self.vx, self.vy,
-                                   self.x_offset, self.y_offset, with_distance=self._with_distance)
+                                   self.x_offset, self.y_offset, with_distance=self._with_distance, num_voxels_dev=num_voxels_dev)
 
     def _forward_torch(self, features, num_voxels, coors):
         """The same in torch ops, any device, any number of PFN layers, train or eval mode."""
@@ -120,16 +126,21 @@ class PointPillarsScatter(nn.Module):
         self.name = "PointPillarsScatter"
         self.nchannels = num_input_features
 
-    def forward(self, voxel_features, coords, batch_size, input_shape):
-        """voxel_features (N, C), coords (N, 4) [b, z, y, x], input_shape [nx, ny, ...] -> (batch_size, C, ny, nx)."""
+    def forward(self, voxel_features, coords, batch_size, input_shape, num_voxels_dev=None):
+        """voxel_features (N, C), coords (N, 4) [b, z, y, x], input_shape [nx, ny, ...] -> (batch_size, C, ny, nx).
+        num_voxels_dev (device int32[1]): capacity form -- rows at or beyond it reach neither the canvas nor a gradient."""
         self.nx, self.ny = int(input_shape[0]), int(input_shape[1])
+        kw = {} if num_voxels_dev is None else dict(num_voxels_dev=num_voxels_dev)
         if voxel_features.is_cuda and voxel_features.shape[1] == ops.PILLAR_CHANNELS and voxel_features.requires_grad:
             return ops.pillar_scatter_train(voxel_features.float().contiguous(), coords.int().contiguous(), int(batch_size), self.ny,
-                                            self.nx)
-        if (voxel_features.is_cuda and voxel_features.shape[1] == ops.PILLAR_CHANNELS and not self.training
-                and not voxel_features.requires_grad):
+                                            self.nx, **kw)
+        if (voxel_features.is_cuda and voxel_features.shape[1] == ops.PILLAR_CHANNELS and not voxel_features.requires_grad
+                and (not self.training or num_voxels_dev is not None)):
             return ops.pillar_scatter(voxel_features.float().contiguous(), coords.int().contiguous(), int(batch_size), self.ny,
-                                      self.nx)
+                                      self.nx, **kw)
+        if num_voxels_dev is not None:
+            raise ValueError("PointPillarsScatter: capacity form (num_voxels_dev) needs the device path (%d-channel device features)"
+                             % ops.PILLAR_CHANNELS)
         return self._forward_torch(voxel_features, coords, int(batch_size))
 
     def _forward_torch(self, voxel_features, coords, batch_size):

@@ -239,6 +239,7 @@ SIGNATURES = {
     "sessd_assign_targets": (i32, [vp, i32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, sz, vp]),
     "sessd_assign_targets_batch_workspace_bytes": (sz, [vp]),
     "sessd_assign_targets_batch": (i32, [vp, vp, vp, vp, vp, vp, sz, vp]),
+    "sessd_draw_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
     "sessd_odiou3d": (i32, [vp, vp, i32, vp, vp, vp]),
     "sessd_adam_ema_step": (i32, [vp, vp, vp, vp, vp, sz, f64, f64, f64, f64, f64, i32, vp, f64, vp]),
     "sessd_one_cycle_args": (i32, [vp, i32, f64, f64, f64, f64, f64, f64, f64, f64, vp, vp, vp]),

@@ -25,7 +25,7 @@ def kitti_3class_rpn_model():
     """The model dict of the reference's three-class config (examples/second/configs/
     kitti_all_vfev3_spmiddlefhd_rpn1_mghead_syncbn.py:62-115): the three one-class tasks on the SECOND-style RPN neck (one block
     of 1 + 5 3x3 layers, one stride-1 up-sampler) instead of SSFA. Anchors: kitti_3class_anchors(). VoxelNet.forward(example, is_ema=[False, None]) returns its
-    supervised loss; no TrainStep for it yet."""
+    supervised loss; sessd_hip.train.SupervisedTrainStep is its iteration."""
     m = kitti_car_model(tasks=KITTI_3CLASS_TASKS)
     m["neck"] = dict(type="RPN", layer_nums=[5], ds_layer_strides=[1], ds_num_filters=[128], us_layer_strides=[1],
                      us_num_filters=[128], num_input_features=128, norm_cfg=None, logger=logging.getLogger("RPN"))

@@ -237,6 +237,131 @@ def voxelize_frames(points_list, voxel_size, coors_range, max_points, max_voxels
     return dict(voxels=voxels, coors=coors, num_points=nump, mean=mean, prefix=prefix, hash=h, grid=grid)
 
 
+def voxelize_staged(staged, voxel_size, coors_range, max_points, max_voxels, out=None):
+    """voxelize_frames on clouds that are staged already: staged (B, P, 4) float32, every frame padded to P rows with
+    out-of-range rows (sessd_stage_points, DrawBatch). Same dict, same bits; no kernel of its own (sessd_voxelize_frames).
+    out: a dict whose tensors are written in place of fresh ones -- voxels (B * max_voxels, max_points, 4), coors or coordinates
+    (B * max_voxels, 4) int32, num_points (B * max_voxels) int32, prefix (B + 1) int32 with prefix[0] == 0, optionally mean
+    (B * max_voxels, 4) and hash (a VoxelHash over B * P items); with all of them given a call allocates nothing after the
+    first (the workspace is cached). Rows at or beyond prefix[B] are unspecified (not written)."""
+    _req(staged, torch.float32, "staged")
+    if staged.dim() != 3 or staged.shape[2] != 4 or staged.shape[0] < 1 or staged.shape[1] < 1:
+        raise ValueError("voxelize_staged: staged points must be (B, P, 4) with B, P >= 1")
+    dev = staged.device
+    B, P = int(staged.shape[0]), int(staged.shape[1])
+    max_points, max_voxels = int(max_points), int(max_voxels)
+    vs = torch.tensor(voxel_size, dtype=torch.float32)
+    cr = torch.tensor(coors_range, dtype=torch.float32)
+    grid = torch.round((cr[3:] - cr[:3]) / vs).to(torch.int32)
+    cap = B * max_voxels
+    out = {} if out is None else out
+    coors_key = "coordinates" if "coordinates" in out else "coors"
+    want = dict(voxels=((cap, max_points, 4), torch.float32), num_points=((cap,), torch.int32), prefix=((B + 1,), torch.int32),
+                mean=((cap, 4), torch.float32))
+    want[coors_key] = ((cap, 4), torch.int32)
+    got = {}
+    for k, (shape, dt) in want.items():
+        t = out.get(k)
+        if t is None:
+            if k == "mean" and out:   # a caller that brings its own tensors and no mean does not want one
+                got[k] = None
+                continue
+            t = torch.zeros(shape, dtype=dt, device=dev) if k == "prefix" else torch.empty(shape, dtype=dt, device=dev)
+        elif not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("voxelize_staged: out[%r] must be a contiguous %s device tensor of shape %s, got %s %s %s"
+                             % (k, dt, shape, t.device, t.dtype, tuple(t.shape)))
+        got[k] = t
+    h = out.get("hash")
+    if h is None:
+        h = VoxelHash(P * B, dev)
+    elif h.capacity < 2 * P * B:
+        raise ValueError("voxelize_staged: out['hash'] holds %d slots, %d needed" % (h.capacity, 2 * P * B))
+    h.clear()
+    ws = workspace(lib.sessd_voxelize_frames_workspace_bytes(h.capacity, B, P, max_points, max_voxels), dev, "voxelize_frames")
+    check(lib.sessd_voxelize_frames(staged.data_ptr(), B, P, 4, cr.data_ptr(), vs.data_ptr(), grid.data_ptr(), max_points, max_voxels,
+                                    h.keys.data_ptr(), h.vals.data_ptr(), h.capacity, got["voxels"].data_ptr(), got[coors_key].data_ptr(),
+                                    4, got["num_points"].data_ptr(), _p(got["mean"]), got["prefix"].data_ptr(), ws.data_ptr(), ws.numel(),
+                                    _stream()), "voxelize_frames")
+    return dict(voxels=got["voxels"], coors=got[coors_key], num_points=got["num_points"], mean=got["mean"], prefix=got["prefix"], hash=h,
+                grid=grid)
+
+
+DRAW_MAX_GT = 128   # sessd_draw_batch: box rows per scene (one 128-thread block per frame)
+
+
+class DrawBatch:
+    """One training batch's clouds and ground truth drawn from resident scene tables in two launches (sessd_draw_batch): the global
+    augmentation (flip about x, rotation about z, scaling) of points and boxes and the ground-truth range filter, for every frame of
+    the batch, nothing read back. Tables (device, kept here): pool_points (S, P, 4) float32 with pool_point_count (S) int32;
+    pool_boxes (S, G, 7) float32, pool_classes (S, G) int32, pool_box_count (S) int32; choice (T, B) int32 scene per slot and
+    iteration; par (T, B, 5) float32 rows [flipped, cos, sin, rotation, scale]. range_xy: [x_lo, y_lo, x_hi, y_hi]. The outputs
+    -- staged (B, P, 4), gt_boxes (B, G, 7), gt_classes (B, G), gt_count (B), transformation (B, 5) -- are allocated here, once:
+    usable inside a captured graph."""
+
+    _OUT = ("staged", "gt_boxes", "gt_classes", "gt_count", "transformation")
+
+    def __init__(self, pool_points, pool_point_count, pool_boxes, pool_classes, pool_box_count, choice, par, range_xy):
+        f32, i32 = torch.float32, torch.int32
+        if pool_points.dim() != 3 or pool_boxes.dim() != 3 or choice.dim() != 2:
+            raise ValueError("DrawBatch: pool_points (S, P, 4), pool_boxes (S, G, 7), choice (T, B) expected")
+        S, P = int(pool_points.shape[0]), int(pool_points.shape[1])
+        G, (T, B) = int(pool_boxes.shape[1]), (int(v) for v in choice.shape)
+        if G > DRAW_MAX_GT:
+            raise ValueError("DrawBatch holds at most %d boxes per scene, got %d" % (DRAW_MAX_GT, G))
+        self.dev = pool_points.device
+        self.S, self.P, self.G, self.T, self.B = S, P, G, T, B
+        for v, name, dt, shape in ((pool_points, "pool_points", f32, (S, P, 4)), (pool_point_count, "pool_point_count", i32, (S,)),
+                                   (pool_boxes, "pool_boxes", f32, (S, G, 7)), (pool_classes, "pool_classes", i32, (S, G)),
+                                   (pool_box_count, "pool_box_count", i32, (S,)), (choice, "choice", i32, (T, B)),
+                                   (par, "par", f32, (T, B, 5))):
+            self._check(v, name, dt, shape)
+        if min(S, P, G, T, B) < 1:
+            raise ValueError("DrawBatch: S, P, G, T and B must be at least 1")
+        r = [float(v) for v in range_xy]
+        if len(r) != 4:
+            raise ValueError("DrawBatch: range_xy is [x_lo, y_lo, x_hi, y_hi]")
+        self._range = (ctypes.c_float * 4)(*r)
+        self.tables = (pool_points, pool_point_count, pool_boxes, pool_classes, pool_box_count, choice, par)
+        self.out = dict(staged=torch.zeros((B, P, 4), dtype=f32, device=self.dev), gt_boxes=torch.zeros((B, G, 7), dtype=f32, device=self.dev),
+                        gt_classes=torch.zeros((B, G), dtype=i32, device=self.dev), gt_count=torch.zeros((B,), dtype=i32, device=self.dev),
+                        transformation=torch.zeros((B, 5), dtype=f32, device=self.dev))
+        self.cursor = 0
+
+    def _check(self, v, name, dtype, shape):
+        if not v.is_cuda or v.device != self.dev or v.dtype != dtype or tuple(v.shape) != shape or not v.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s, got %s %s %s"
+                             % (name, dtype, shape, self.dev if self.dev.type == "cuda" else "the HIP device", v.device, v.dtype,
+                                tuple(v.shape)))
+
+    def run(self, it=None, iter_dev=None, out=None):
+        """Draw batch `it` (default: the next one; row it mod T of choice / par), or the one a DEVICE int32[1] counter `iter_dev`
+        names when the launch executes. out: dict with any of staged / gt_boxes / gt_classes / gt_count / transformation written
+        in place of this object's own. Returns the dict of the five outputs; every element of each is written."""
+        B, P, G = self.B, self.P, self.G
+        shapes = dict(staged=((B, P, 4), torch.float32), gt_boxes=((B, G, 7), torch.float32), gt_classes=((B, G), torch.int32),
+                      gt_count=((B,), torch.int32), transformation=((B, 5), torch.float32))
+        res = {}
+        for k in self._OUT:
+            v = None if out is None else out.get(k)
+            if v is None:
+                v = self.out[k]
+            else:
+                self._check(v, "out[%r]" % k, shapes[k][1], shapes[k][0])
+            res[k] = v
+        if iter_dev is not None:
+            self._check(iter_dev, "iter_dev", torch.int32, tuple(iter_dev.shape) if iter_dev.numel() == 1 else (1,))
+            it = 0
+        else:
+            it = self.cursor if it is None else int(it)
+            self.cursor = it + 1
+        t = self.tables
+        check(lib.sessd_draw_batch(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), t[4].data_ptr(), t[5].data_ptr(),
+                                   t[6].data_ptr(), self.S, P, G, self.T, B, _addr(self._range), it % self.T, _p(iter_dev) or None,
+                                   res["staged"].data_ptr(), res["gt_boxes"].data_ptr(), res["gt_classes"].data_ptr(),
+                                   res["gt_count"].data_ptr(), res["transformation"].data_ptr(), _stream()), "draw_batch")
+        return res
+
+
 def vfe_mean(voxels, num_points, num_features=4, num_voxels_dev=None):
     _req(voxels, torch.float32, "voxels")
     _req(num_points, torch.int32, "num_points")

@@ -13,6 +13,9 @@ What is here
                       fused update, in the order of trainer_sessd.py:250-275,340-357; `capture()` / `replay()`: the whole
                       iteration as ONE hipGraph (capacity-sized inputs with device-side counts, the OneCycle schedule and the
                       Adam constants computed on the device: sessd_one_cycle_args) -- nothing in it reads the host
+  * SupervisedTrainStep  the iteration of the configs without a teacher (three-class SECOND, PointPillars): model.forward_loss ->
+                      backward -> all-reduce -> the same fused update without the EMA; capture() / replay() as TrainStep
+  * check_trainable   which layers of a model would leave the HIP kernels for their torch modules in a train-mode pass
   * capacity_example  pads a collated example to fixed row capacities and adds the device-side voxel counts that switch the
                       sparse module path to its capacity mode (spconv.SparseConvTensor(n_dev=...))
 The sparse backbone (spconv.IndiceConvFunction) and the twelve dense convs of the neck (ops.Conv2dFunction) run forward
@@ -203,6 +206,249 @@ def consistency_rampup(epoch, max_epochs=60):
         return 1.0
     phase = 1.0 - min(max(float(epoch), 0.0), 15.0) / 15.0
     return float(math.exp(-5.0 * phase * phase))
+
+
+def _sparse_flag(model):
+    return getattr(getattr(model, "backbone", None), "last_err", None)
+
+
+def check_trainable(model, example):
+    """Names of the layers of `model` that would leave the HIP kernels for their torch modules in a train-mode pass over
+    `example` (a report: nothing is raised, nothing is changed -- the BatchNorm running statistics the probing pass touches are
+    put back). An empty list means reader, scatter, neck, head and loss all run on the library; at full PointPillars size the
+    neck's narrow maps need `model.neck.train_any_width = True`."""
+    from torch import nn
+    leaves = (nn.Conv2d, nn.ConvTranspose2d, nn.Linear, nn.modules.batchnorm._BatchNorm)
+    fired, hooks = [], []
+    for name, m in model.named_modules():
+        if isinstance(m, leaves):
+            hooks.append(m.register_forward_hook(lambda _m, _i, _o, name=name: fired.append(name)))
+    was_training = model.training
+    state = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    out = []
+    try:
+        model.train()
+        reader = getattr(model, "reader", None)
+        if hasattr(reader, "on_device_train_path") and not reader.on_device_train_path(example["voxels"]):
+            out.append("reader (torch formulation: more than one PFN layer, another width or norm layer, or a CPU tensor)")
+        with ops.deferred_batch_counts():
+            if hasattr(model, "forward_loss") and all(k in example for k in ("labels", "reg_targets", "anchors")):
+                keep = getattr(model, "supervised", None)
+                if keep is False:
+                    model.supervised = True
+                try:
+                    _, rec = model.forward_loss(example)
+                finally:
+                    if keep is False:
+                        model.supervised = False
+                if not torch.is_tensor(rec):
+                    out.append("bbox_head loss (torch formulation: bbox_head.supervised_loss_covers is false)")
+            else:
+                model.forward_preds(example) if hasattr(model, "forward_preds") else model(example, return_loss=False)
+    finally:
+        for h in hooks:
+            h.remove()
+        with torch.no_grad():
+            for k, v in model.state_dict().items():
+                v.copy_(state[k])
+        model.train(was_training)
+        ops.bump_param_generation()
+    seen = set()
+    return out + [n for n in fired if not (n in seen or seen.add(n))]
+
+
+class SupervisedTrainStep:
+    """One supervised iteration -- no teacher, no consistency term -- of the reference's three-class SECOND and PointPillars
+    configs: model.forward_loss (reader, backbone / scatter, neck, head and sessd_supervised_loss) -> backward -> gradients
+    packed -> all-reduce -> clip + Adam with true weight decay on the OneCycle schedule (FusedAdamEMA without a teacher).
+    `model` has forward_loss(example, unit_grad) -> (total, record): VoxelNet, or a PointPillars model switched to
+    `supervised = True`. capture() / replay() run the whole iteration as one hipGraph on a capacity-form example, as
+    TrainStep does."""
+
+    def __init__(self, model, total_steps, weight_decay=0.01, max_grad_norm=35.0, lr_max=3e-3, moms=(0.95, 0.85), div_factor=10.0,
+                 pct_start=0.4):
+        if not hasattr(model, "forward_loss"):
+            raise ValueError("SupervisedTrainStep needs a model with forward_loss(example, unit_grad) (VoxelNet, PointPillars)")
+        if getattr(model, "supervised", True) is not True:
+            raise ValueError("SupervisedTrainStep: this %s is inference only; switch it to model.supervised = True first"
+                             % type(model).__name__)
+        self.model = model
+        self.total_steps = int(total_steps)
+        self.sched = dict(lr_max=lr_max, moms=moms, div_factor=div_factor, pct_start=pct_start)
+        self.flat = FlatParams(model)
+        self.opt = FusedAdamEMA(self.flat, None, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        self.global_step = 0
+        self.graph = None
+        self.repack = ops.RepackRegistry()
+        self.sync_bn = None          # as TrainStep: None = on exactly when the process group has more than one rank
+        self.sync_bn_group = None
+        self.sparse_overflow = None  # sticky device int32: a sparse level capacity overflowed in some pass since the last check
+        self.last_record = None
+        self.last_losses = None
+        self.static_loss = None
+
+    def _world(self):
+        return dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
+
+    def _collective(self):
+        from .dist import collectives_enabled
+        return collectives_enabled()
+
+    def _fwd_bwd(self, example):
+        """Everything of an iteration before the ranks exchange gradients. Returns the detached loss."""
+        self.model.train()
+        prev_sync = ops.sync_bn_state()
+        on = self.sync_bn if self.sync_bn is not None else self._collective()
+        if self.sync_bn_group is not None:
+            ops.set_sync_bn(on, group=self.sync_bn_group)
+        else:
+            ops.set_sync_bn(on)
+        try:
+            self.flat.release_grads()
+            with ops.batched_repack(self.repack), ops.deferred_batch_counts():
+                loss, rec = self.model.forward_loss(example, unit_grad=True)
+                self._note_sparse_overflow()
+            if torch.is_tensor(rec):
+                self.last_record, self.last_losses = rec, None
+            else:
+                self.last_record, self.last_losses = None, rec
+            with ops.batched_repack(self.repack):
+                loss.backward()
+            self.flat.gather_grads()
+            return loss.detach()
+        finally:
+            ops.restore_sync_bn(prev_sync)
+
+    def _note_sparse_overflow(self):
+        f = _sparse_flag(self.model)
+        if f is None:
+            return
+        if self.sparse_overflow is None:
+            self.sparse_overflow = torch.zeros(1, dtype=torch.int32, device=f.device)
+        self.sparse_overflow.bitwise_or_((f.detach().reshape(1) != 0).to(torch.int32))
+
+    def _update(self, device_schedule):
+        if device_schedule:
+            self.opt.step_dev(self.total_steps, **self.sched)
+            return None, None
+        lr, mom = one_cycle(self.global_step, self.total_steps, **self.sched)
+        self.opt.step(lr, mom, self.global_step)
+        return lr, mom
+
+    def _iteration(self, example, device_schedule):
+        loss = self._fwd_bwd(example)
+        allreduce_flat(self.flat.grad)
+        lr, mom = self._update(device_schedule)
+        return loss, lr, mom
+
+    def __call__(self, example, device_schedule=False):
+        """One eager iteration -> (loss, lr, mom); device_schedule=True evaluates the schedule on the device from the device
+        iteration counter (the arithmetic a captured iteration replays) and returns (loss, None, None)."""
+        if device_schedule and int(self.opt.global_step_dev.item()) != self.global_step:
+            self.opt.global_step_dev.fill_(self.global_step)
+        out = self._iteration(example, device_schedule)
+        self.global_step += 1
+        if not device_schedule:
+            self.opt.global_step_dev.fill_(self.global_step)
+        return out
+
+    def check_overflow(self):
+        """Synchronising: raise if a pass since the last check overflowed a sparse level capacity. Re-arms the flag."""
+        sp = int(self.sparse_overflow.item()) if self.sparse_overflow is not None else 0
+        if sp:
+            self.sparse_overflow.zero_()
+            raise RuntimeError("sparse level capacity overflow in at least one iteration since the last check: those iterations "
+                               "trained on truncated sparse tensors; raise spconv.CAPACITY_GROWTH or the voxel capacity")
+
+    def record(self):
+        """The last iteration's log terms as the dict bbox_head.loss_supervised returns (one host read)."""
+        self.check_overflow()
+        if self.last_record is None:
+            return self.last_losses
+        return self.model.bbox_head.supervised_record_to_dict(self.last_record)
+
+    def capture(self, example, warmup=2):
+        """Capture forward / loss / backward / all-reduce / update on `example` as one graph (two around the eager all-reduce when
+        collectives are on). `example` is in capacity form (`num_voxels_dev`: fixed shapes, the live count on the device) and the
+        loss must be the device op: nothing in the graph may read the host. Runs `warmup` real iterations first (they count).
+        Later batches are written INTO the example's tensors before replay()."""
+        if "num_voxels_dev" not in example:
+            raise ValueError("capture() needs a capacity-form example: fixed-size voxel tables with the live count in "
+                             "example['num_voxels_dev'] (sessd_hip.train.capacity_example, trainloop.SupervisedBatcher)")
+        if self._collective() and (self.sync_bn if self.sync_bn is not None else True):
+            raise RuntimeError("SupervisedTrainStep.capture() at world size %d with SyncBN: the BatchNorm all-reduces sit inside the "
+                               "passes and cannot be captured; run the iteration eagerly or set step.sync_bn = False" % self._world())
+        if not getattr(self.model, "device_loss", True):
+            raise ValueError("capture(): model.device_loss is off; the torch formulation of the loss reads the host")
+        not_covered = ("capture(): the supervised loss of this head is not the device op (bbox_head.supervised_loss_covers is "
+                       "false: see its conditions); the torch formulation reads the host and cannot be captured")
+        if not self._loss_covered(example):
+            raise ValueError(not_covered)
+        self.static_example = example
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self(example, device_schedule=True)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        if warmup and self.last_record is None:   # the head's real outputs said otherwise than the shapes promised
+            raise ValueError(not_covered)
+        self.opt.global_step_dev.fill_(self.global_step)
+        dev = self.flat.data.device
+        self.static_loss = torch.zeros((), dtype=torch.float32, device=dev)   # outside the graph's pool, as in TrainStep.capture
+        if self.sparse_overflow is None and _sparse_flag(self.model) is not None:
+            self.sparse_overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+        ops.new_capture_epoch()
+        self.repack.prepare()
+        self.repack.gen = -1
+        if self._collective():   # two graphs split where the ranks talk; replay() issues the all-reduce eagerly between them
+            ga = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(ga):
+                loss = self._fwd_bwd(example)
+                self.static_loss.copy_(loss)
+            gb = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gb, pool=ga.pool()):
+                self._update(True)
+            self.opt.steps -= 1
+            self.graph = (ga, gb)
+            return self.graph
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            loss, _, _ = self._iteration(example, True)
+            self.static_loss.copy_(loss)
+        self.opt.steps -= 1   # the captured launches did not run
+        self.graph = g
+        return g
+
+    def _loss_covered(self, example):
+        """bbox_head.supervised_loss_covers asked without a pass: on head outputs of the shapes the example's anchors imply (the
+        predicate reads shapes and devices only)."""
+        head = self.model.bbox_head
+        if not all(k in example for k in ("labels", "reg_targets", "anchors")):
+            return False
+        dev = self.flat.data.device
+        T = len(head.num_classes)
+        if len(example["anchors"]) < T:
+            return False
+        B, A = example["anchors"][0].shape[0], example["anchors"][0].shape[1]
+        E = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        return bool(head.supervised_loss_covers(example, [dict(box_preds=E(B, A, 7), cls_preds=E(B, A), dir_cls_preds=E(B, A, 2))
+                                                          for _ in range(T)]))
+
+    def replay(self):
+        """One captured iteration on whatever the static example's tensors hold now. Returns the (device) loss tensor;
+        `last_record` is that iteration's device record."""
+        if isinstance(self.graph, tuple):
+            self.graph[0].replay()
+            allreduce_flat(self.flat.grad)
+            self.graph[1].replay()
+        else:
+            self.graph.replay()
+        self.global_step += 1
+        self.opt.steps += 1
+        ops.bump_param_generation()
+        return self.static_loss
 
 
 class TrainStep:

@@ -14,6 +14,8 @@ ray-cast synthetic scans of sessd_hip.synth with their VISIBLE cars as ground tr
   fit            the loop: load a batch, replay the graph, every `log_every` iterations ONE host read of the 64-float loss record
                  (and of the sticky overflow flags); consistency weight by the reference's sigmoid ramp-up over the first quarter
                  of the run (15 of 60 epochs); returns the log and the sustained samples/s (data path INSIDE the clock).
+  SupervisedBatcher / fit_supervised   the same for the configs without a teacher (three-class SECOND, PointPillars): one view, any
+                 tasks and grid, the batch drawn by sessd_draw_batch instead of per-frame torch arithmetic; train.SupervisedTrainStep
   SyntheticKitti the held-out scans as a KITTI-format validation set: kitti_infos with camera-frame annotations made by the very
                  conversion detections go through (det3d.datasets.kitti.convert_detection_to_kitti_annos), for KittiDataset.evaluation.
 The GT-AUG database sampler and the per-object noise of the reference's Preprocess stay with the host mirror
@@ -305,6 +307,128 @@ def fit(model, pool, iterations=2000, batch=4, lr_max=3e-3, seed=0, log_every=50
     if ema_ref is not None:
         rep["teacher_vs_ema_of_student_maxabs"] = float((ema_ref - step.flat_t.data).abs().max())
         rep["teacher_maxabs"] = float(step.flat_t.data.abs().max())
+    return step, rep
+
+
+class SupervisedBatcher:
+    """Labelled batches for the supervised configs (three-class SECOND, PointPillars: one view, any tasks, any grid) in ONE static
+    capacity-form example, assembled by three device ops per batch whatever its size: ops.DrawBatch (sessd_draw_batch: scene
+    choice, global augmentation of points and boxes, range filter -- DeviceBatcher's torch arithmetic as two launches),
+    ops.voxelize_staged straight into the example's tables, ops.AssignTargets straight into its labels / reg_targets. Nothing
+    reads the host, and nothing is allocated on the device after the first load().
+    pool_points: list of (P_i, 4) float32 clouds; pool_boxes: list of (n_i, 7) ground-truth boxes (n_i <= 128); pool_classes: list
+    of (n_i,) class ids or None (every box is class 1). voxel_generator_cfg: dict(range, voxel_size); max_points per voxel,
+    max_voxels per frame; tasks: as ops.AssignTargets takes them (anchors (A, 7), class_id, matched_threshold,
+    unmatched_threshold); grid_shape: the example's `shape` entry. `iterations` fixes how many batches can be drawn: scene choices
+    and augmentation parameters are drawn here, once, from `seed`, with DeviceBatcher's distributions."""
+
+    def __init__(self, pool_points, pool_boxes, pool_classes, dev, batch, iterations, voxel_generator_cfg, max_points, max_voxels,
+                 tasks, grid_shape, seed=0, augment=True):
+        self.dev, self.B, self.T = torch.device(dev), int(batch), int(iterations)
+        self.max_points, self.max_voxels = int(max_points), int(max_voxels)
+        self.vrange, self.vsize = list(voxel_generator_cfg["range"]), list(voxel_generator_cfg["voxel_size"])
+        S, B, T = len(pool_points), self.B, self.T
+        if S < 1 or len(pool_boxes) != S or (pool_classes is not None and len(pool_classes) != S):
+            raise ValueError("SupervisedBatcher: one cloud, one box array (and one class array) per scene")
+        self.choice_host, self.par_host = self.draw_tables(S, B, T, seed, augment)
+        P = max(1, max(int(p.shape[0]) for p in pool_points))
+        G = max(1, max(int(np.asarray(b).reshape(-1, 7).shape[0]) for b in pool_boxes))
+        pts = np.zeros((S, P, 4), np.float32)
+        boxes, classes = np.zeros((S, G, 7), np.float32), np.zeros((S, G), np.int32)
+        npts, nbox = np.zeros(S, np.int32), np.zeros(S, np.int32)
+        for i in range(S):
+            p, b = np.asarray(pool_points[i], np.float32), np.asarray(pool_boxes[i], np.float32).reshape(-1, 7)
+            pts[i, :len(p)], npts[i] = p, len(p)
+            boxes[i, :len(b)], nbox[i] = b, len(b)
+            classes[i, :len(b)] = 1 if pool_classes is None else np.asarray(pool_classes[i], np.int32)
+        up = lambda a: torch.from_numpy(a).to(self.dev)
+        r = self.vrange
+        self.draw = ops.DrawBatch(up(pts), up(npts), up(boxes), up(classes), up(nbox), up(self.choice_host), up(self.par_host),
+                                  [r[0], r[1], r[3], r[4]])
+        tasks = [dict(t, anchors=torch.as_tensor(t["anchors"], dtype=torch.float32).to(self.dev).contiguous()) for t in tasks]
+        A = int(tasks[0]["anchors"].shape[-2])
+        self.assigner = ops.AssignTargets(B, A, tasks, self.dev, gt_capacity=G)
+        cap = B * self.max_voxels
+        i32, f32 = torch.int32, torch.float32
+        prefix = torch.zeros(B + 1, dtype=i32, device=self.dev)
+        nt = len(tasks)
+        self.example = dict(
+            voxels=torch.zeros((cap, self.max_points, 4), dtype=f32, device=self.dev),
+            coordinates=torch.full((cap, 4), -1, dtype=i32, device=self.dev), num_points=torch.ones(cap, dtype=i32, device=self.dev),
+            prefix=prefix, num_voxels_dev=prefix[B:B + 1], hash=ops.VoxelHash(P * B, self.dev),
+            num_voxels=torch.zeros(B, dtype=torch.int64), shape=[list(grid_shape)] * B, metadata=[{}] * B,
+            anchors=list(self.assigner.anchors), labels=[torch.zeros((B, A), dtype=i32, device=self.dev) for _ in range(nt)],
+            reg_targets=[torch.zeros((B, A, 7), dtype=f32, device=self.dev) for _ in range(nt)],
+            gt_boxes=self.draw.out["gt_boxes"], gt_classes=self.draw.out["gt_classes"], gt_count=self.draw.out["gt_count"],
+            transformation_dev=self.draw.out["transformation"])
+        self.cursor = 0
+
+    @staticmethod
+    def draw_tables(num_scenes, batch, iterations, seed=0, augment=True):
+        """(choice (T, B) int32, par (T, B, 5) float32 rows [flipped, cos, sin, rotation, scale]) drawn from `seed` in the order
+        and with the distributions of DeviceBatcher: flip with probability 1/2, rotation in +-pi/4, scale in 0.95 .. 1.05."""
+        S, B, T = int(num_scenes), int(batch), int(iterations)
+        rng = np.random.RandomState(seed)
+        choice = np.stack([rng.choice(S, B, replace=S < B) for _ in range(T)]).astype(np.int32)
+        flip = (rng.rand(T, B) < 0.5) if augment else np.zeros((T, B), bool)
+        rot = rng.uniform(-math.pi / 4, math.pi / 4, (T, B)) if augment else np.zeros((T, B))
+        scale = rng.uniform(0.95, 1.05, (T, B)) if augment else np.ones((T, B))
+        return choice, np.stack([flip.astype(np.float64), np.cos(rot), np.sin(rot), rot, scale], -1).astype(np.float32)
+
+    @classmethod
+    def from_scene_pool(cls, pool, dev, batch, iterations, voxel_generator_cfg, max_points, max_voxels, tasks, grid_shape, **kw):
+        """A ScenePool's scans with their visible cars as class 1."""
+        return cls(pool.frames, [pool.visible(i) for i in range(len(pool))], None, dev, batch, iterations, voxel_generator_cfg,
+                   max_points, max_voxels, tasks, grid_shape, **kw)
+
+    def load(self, it=None):
+        """Fill the static example with batch `it` (default: the next one): three device ops, no host synchronisation."""
+        it = self.cursor if it is None else int(it)
+        if it >= self.T:
+            raise IndexError("SupervisedBatcher was built for %d iterations" % self.T)
+        self.cursor = it + 1
+        ex = self.example
+        d = self.draw.run(it)
+        ops.voxelize_staged(d["staged"], self.vsize, self.vrange, self.max_points, self.max_voxels, out=ex)
+        self.assigner.run(d["gt_boxes"], d["gt_classes"], d["gt_count"], out=ex)
+        return ex
+
+
+def fit_supervised(model, batcher, iterations, log_every=50, capture=True):
+    """Train `model` (VoxelNet, or PointPillars switched to supervised = True) for `iterations` supervised iterations on fresh
+    batches from a SupervisedBatcher: load a batch, replay the captured iteration (capture=False: an eager one on the device
+    schedule -- the same arithmetic, the same bits), and every `log_every` iterations ONE host read of the loss record. Loader and
+    iteration share one stream. Returns (SupervisedTrainStep, report) with fit()'s timing keys."""
+    step = strain.SupervisedTrainStep(model, total_steps=iterations)
+    ex = batcher.load(0)
+    warm = 1
+    if capture:
+        step.capture(ex, warmup=warm)   # `warm` real iterations on batch 0
+    done = warm if capture else 0
+    log = []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(done, iterations):
+        batcher.load(it)
+        if capture:
+            step.replay()
+        else:
+            step(ex, device_schedule=True)
+        if (it + 1) % log_every == 0 or it + 1 == iterations:
+            rec = step.record()   # the window's one host read (raises on a sparse capacity overflow)
+            row = {"iteration": it + 1, "total": float(rec["total"] if "total" in rec else sum(rec["loss"]))}
+            row.update({k: [float(v) for v in rec[k]] for k in ("loss", "cls_loss_reduced", "loc_loss_reduced", "dir_loss_reduced")})
+            row["num_pos"] = [int(v) for v in rec["num_pos"]]
+            log.append(row)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    n = iterations - done
+    rep = {"iterations": iterations, "batch": batcher.B, "timed_iterations": n, "seconds": dt, "ms_per_iteration": dt / max(1, n) * 1e3,
+           "samples_per_s": n * batcher.B / dt if n else 0.0, "log": log, "scenes": batcher.draw.S, "data_path_overlapped": False,
+           "what": "supervised iterations (forward, sessd_supervised_loss, backward, clip / Adam) %s on FRESH batches: scene "
+                   "choice + global augmentation + range filter (sessd_draw_batch), voxelization and target assignment on the "
+                   "device inside the clock, one host read of the loss record per %d iterations"
+                   % ("replayed from one captured graph" if capture else "run eagerly", log_every)}
     return step, rep
 
 
